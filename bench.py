@@ -18,18 +18,23 @@ time 10^5 steps per chain after 10^4 of warm-up, and the driver's --warmup 5 --s
 time 10^5 after 2.5 x 10^4.  (The reference runs its 10^5 steps per chain as one loop,
 grid_chain_sec11.py:342, which the library runs as one launch; a launch lasts as long as
 its slowest chain, a wait that shrinks with longer launches: profiles/r05/launch_length/.)
-At N = 1 the line also carries "secondary": the same warm-up and timed launch COUNTS at
-1,000 steps per launch (the protocol of rounds 1-5, chains earlier in their burn-in and
-therefore faster), on a fresh set of chains after the headline measurement.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Extra fields: "roofline" (dominant kernel, algorithmic bytes of SURVEY.md §8d per launch /
-mean HIP-event launch time vs 8 TB/s), "cpu_baseline" (the GerryChain-equivalent Python
-proxy, oracle/reference_proxy.py, one chain per process on every usable host core) and
-"cpu_native" (the C oracle, one chain per thread on the same cores), rank 0 at N=1 only,
-bounded samples of the same workload.
+A plain run sets up, warms up, times the K launches and prints the line; its "roofline"
+(dominant kernel, algorithmic bytes of SURVEY.md §8d per launch / mean HIP-event launch time
+vs 8 TB/s) and PMC fields come from the timed launches' own counters and the stored
+profiles, no further runs.  ``--dump-outputs DIR`` also writes what the last timed launch
+left (dump_outputs).  Everything that takes runs of its own is behind ``--full``:
+"parity_check" (a spread of the benched chains re-run on the C oracle and compared bit for
+bit; --check-chains), at N = 1 "secondary" (the same warm-up and timed launch COUNTS at
+1,000 steps per launch, the protocol of rounds 1-5, chains earlier in their burn-in and
+therefore faster, on a fresh set of chains after the headline measurement;
+--secondary-inner), and, rank 0 at N = 1 only, bounded samples of the same workload on the
+host: "cpu_baseline" (the GerryChain-equivalent Python proxy, oracle/reference_proxy.py, one
+chain per process on every usable host core) and "cpu_native" (the C oracle, one chain per
+thread on the same cores; --no-cpu-baseline, --cpu-seconds).
 """
 from __future__ import annotations
 
@@ -269,6 +274,33 @@ def flipwalk_env():
     return {k: v for k, v in sorted(os.environ.items()) if k.startswith("FLIPWALK_")}
 
 
+# ------------------------------------------------------------------ output dump
+DUMP_LABEL_CHAINS = 512  # x 10,000 nodes x 4 B = 20 MB of the 64 MB a dump may take
+
+
+def dump_outputs(path, ch, st, hist_cut, hist_b):
+    """Write what the last timed launch left, the arrays a caller of Chains.run reads back,
+    as ``path``/<name>.npy: every stats field and the district populations of every chain
+    (float64: the counters stay below 2^53, sum_invb is fp64 already), the merged histograms
+    (float64) and the final plans of a fixed sample of chains (float32; ``label_chains``
+    holds their local indices, drawn once from a fixed seed, so two builds dump the same
+    chains).  Trajectories depend only on the arguments, so equal arguments give equal files."""
+    os.makedirs(path, exist_ok=True)
+    out = {"stats_" + f: np.asarray(st[f], np.float64) for f in STAT_FIELDS}
+    out["pops"] = ch.pops().astype(np.float64)
+    out["hist_cut"] = hist_cut.astype(np.float64)
+    out["hist_b"] = hist_b.astype(np.float64)
+    n = ch.n_chains
+    per_chain = 8 * (len(STAT_FIELDS) + ch.k)
+    room = 60e6 - n * per_chain - 8 * (hist_cut.size + hist_b.size)
+    take = int(max(1, min(n, DUMP_LABEL_CHAINS, room // (4 * ch.dgraph.n))))
+    pick = np.sort(np.random.default_rng(20240229).choice(n, size=take, replace=False))
+    out["label_chains"] = pick.astype(np.float64)
+    out["labels"] = ch.labels()[pick].astype(np.float32)
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
 # ------------------------------------------------------------------ PMC profiles
 def pmc_key(config, order, chains, inner, warmup, steps, chain_id0=0, resumed=0):
     """Name of the PMC summary of one bench protocol (profiles/pmc/<key>.json): workload,
@@ -322,10 +354,18 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need, each a run of its "
+                         "own: the oracle parity check (--check-chains), the \"secondary\" "
+                         "line (--secondary-inner) and the CPU baselines (--no-cpu-baseline, "
+                         "--cpu-seconds)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed launch left (stats, populations, "
+                         "merged histograms, a fixed sample of final plans) as DIR/<name>.npy")
     ap.add_argument("--inner", type=int, default=5000,
                     help="flip steps per chain per launch (see the module docstring)")
     ap.add_argument("--secondary-inner", type=int, default=1000,
-                    help="N=1: also time the same launch counts at this many steps per launch "
+                    help="--full, N=1: also time the same launch counts at this many steps per launch "
                          "(the round 1-5 protocol) on fresh chains -> \"secondary\" (0 = off)")
     ap.add_argument("--config", default="c3", choices=["c3", "c2", "c4", "c5", "frank"],
                     help="workload (flipcomplexityempirical_amd/workloads.py); the driver's line "
@@ -350,9 +390,10 @@ def main():
     ap.add_argument("--proposal", default=None)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the cpu_baseline / cpu_native legs")
     ap.add_argument("--check-chains", type=int, default=16,
-                    help="chains per rank re-run on the C oracle after the timed region and "
+                    help="--full: chains per rank re-run on the C oracle after the timed region and "
                          "compared bit for bit (parity_check; 0 = off)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process group for N>1 (nccl = RCCL over xGMI; gloo for rehearsals)")
@@ -472,7 +513,7 @@ def main():
     # checker leg, after the timed region: every rank re-runs a spread of its chains on the
     # C oracle; the line carries the totals over ranks
     pc = None
-    if args.check_chains > 0:
+    if args.full and args.check_chains > 0:
         pc = parity_check(w, ch, bounds, base, args.seed, lo,
                           resumed + (args.warmup + args.steps) * args.inner, args.check_chains,
                           host_cores()[0])
@@ -491,6 +532,8 @@ def main():
 
     if args.save_checkpoint:
         ch.save_checkpoint(args.save_checkpoint)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ch, st1_arr, hist_cut, hist_b)
     if args.save_hist:
         fin = np.stack([st1_arr["cut"], st1_arr["bnodes"]]).astype(np.int64)
         if dist is not None:
@@ -613,12 +656,13 @@ def main():
             "mean_bnodes": float(st1_arr["bnodes"].mean()),
             "hist_yields": int(hist_cut.sum()),
         }
-        if world == 1 and not args.shard and args.secondary_inner > 0 and not args.resume \
+        if args.full and world == 1 and not args.shard and args.secondary_inner > 0 \
+                and not args.resume \
                 and not args.maps and args.secondary_inner != args.inner:
             out["secondary"] = secondary_line(dg, w, chains, init, proposal, bounds, base,
                                               args.seed, lo, args.secondary_inner, args.warmup,
                                               args.steps)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             b0 = float(np.ravel(base)[0])
             if not args.shard:
                 out["cpu_baseline"] = cpu_baseline(args.config, w.desc, percent, b0, args.seed,

@@ -8,7 +8,8 @@
 #   tests                 every -m gpu test
 #   tests:EXPR            the -m gpu tests selected by -k EXPR (',' for ' ')
 #   smoke                 __graft_entry__.smoke()
-#   bench[:ARGS]          one bench.py line (ARGS with ',' for ' ') -> OUT/bench.jsonl
+#   bench[:ARGS]          one bench.py line (ARGS with ',' for ' '; --full for the checker,
+#                         secondary and CPU legs) -> OUT/bench.jsonl
 #   ck_c5                 C5 shard 0/8 advanced 10^5 steps, checkpoint /tmp/ck_c5_100k.npz
 #   prof_c5               kernel trace + PMC of the C5 shard resumed from that checkpoint
 #   prof_c4 / prof_c3 / prof_c2 / prof_c3s8
@@ -111,7 +112,7 @@ run_task() {
       grep -v amdgpu.ids $O/stamps_c4.txt ;;
     steady)
       for a in "--config c3" "--config c2" "--config c4" "--config c5 --shard 0/8" "--config frank" "--config c3 --shard 0/8"; do
-        timeout -k 10 300 python -u bench.py $a --inner 5000 --warmup 2 --steps 20 --no-cpu-baseline --check-chains 2 > $O/one.json 2> $O/one.err || { echo "$a failed"; tail -5 $O/one.err; return 1; }
+        timeout -k 10 300 python -u bench.py $a --inner 5000 --warmup 2 --steps 20 --full --no-cpu-baseline --check-chains 2 > $O/one.json 2> $O/one.err || { echo "$a failed"; tail -5 $O/one.err; return 1; }
         tail -1 $O/one.json >> $O/steady.jsonl
         line $O/one.json "$a"
       done ;;
@@ -124,21 +125,21 @@ run_task() {
           # a lib may carry one environment setting: name@VAR=VALUE
           local lib=${v%%@*} envs=""
           [ "$lib" != "$v" ] && envs=${v#*@}
-          env $envs FLIPWALK_LIB=$PWD/ab/lib_$lib.so timeout -k 10 300 python -u bench.py $args --no-cpu-baseline > $O/one.json 2> $O/one.err || { echo "$v failed"; tail -5 $O/one.err; return 1; }
+          env $envs FLIPWALK_LIB=$PWD/ab/lib_$lib.so timeout -k 10 300 python -u bench.py $args --full --no-cpu-baseline > $O/one.json 2> $O/one.err || { echo "$v failed"; tail -5 $O/one.err; return 1; }
           python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); pc=d.get('parity_check') or {}; print(json.dumps({'tag': sys.argv[4], 'lib': sys.argv[2], 'rep': int(sys.argv[3]), 'value': d['value'], 'kernel_ms': d['kernel_ms'], 'parity': [pc.get('equal'), pc.get('chains')]}))" $O/one.json $v $rep $tag | tee -a $O/ab_$tag.jsonl
         done
       done ;;
     shards_c5)  # the 8-GPU C5 job emulated shard by shard at the steady-state protocol
-      timeout -k 10 900 bash scripts/shards.sh 8 "--config c5 --steps 20 --warmup 5 --check-chains 2" c5 > $O/shards_c5.log 2>&1 || { tail -5 $O/shards_c5.log; return 1; }
+      timeout -k 10 900 bash scripts/shards.sh 8 "--config c5 --steps 20 --warmup 5 --full --check-chains 2" c5 > $O/shards_c5.log 2>&1 || { tail -5 $O/shards_c5.log; return 1; }
       tail -10 $O/shards_c5.log ;;
     shards_c3)  # the 8-GPU C3 job emulated shard by shard on the driver protocol
-      timeout -k 10 600 bash scripts/shards.sh 8 "--config c3 --steps 20 --warmup 5 --check-chains 2" c3 > $O/shards_c3.log 2>&1 || { tail -5 $O/shards_c3.log; return 1; }
+      timeout -k 10 600 bash scripts/shards.sh 8 "--config c3 --steps 20 --warmup 5 --full --check-chains 2" c3 > $O/shards_c3.log 2>&1 || { tail -5 $O/shards_c3.log; return 1; }
       tail -10 $O/shards_c3.log ;;
     shards_c3s)  # the 8-GPU C3 job emulated shard by shard at the steady state
-      timeout -k 10 900 bash scripts/shards.sh 8 "--config c3 --inner 5000 --steps 20 --warmup 2 --check-chains 2" c3steady > $O/shards_c3steady.log 2>&1 || { tail -5 $O/shards_c3steady.log; return 1; }
+      timeout -k 10 900 bash scripts/shards.sh 8 "--config c3 --inner 5000 --steps 20 --warmup 2 --full --check-chains 2" c3steady > $O/shards_c3steady.log 2>&1 || { tail -5 $O/shards_c3steady.log; return 1; }
       tail -10 $O/shards_c3steady.log ;;
     multi)
-      timeout -k 10 300 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29512 bench.py --config c3 --chains 8192 --steps 2 --warmup 1 --backend gloo --same-device --no-cpu-baseline --check-chains 4 > $O/multi.json 2> $O/multi.err || { tail -20 $O/multi.err; return 1; }
+      timeout -k 10 300 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29512 bench.py --config c3 --chains 8192 --steps 2 --warmup 1 --backend gloo --same-device --full --no-cpu-baseline --check-chains 4 > $O/multi.json 2> $O/multi.err || { tail -20 $O/multi.err; return 1; }
       tail -1 $O/multi.json ;;
     *) echo "unknown task $t"; return 2 ;;
   esac

@@ -210,7 +210,7 @@ def test_bench_under_torchrun_two_ranks(tmp_path, gpu_lib):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     args = ["--config", "c3", "--chains", "8192", "--steps", "2", "--warmup", "1",
-            "--inner", "300", "--no-cpu-baseline", "--check-chains", "4"]
+            "--inner", "300", "--full", "--no-cpu-baseline", "--check-chains", "4"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     h2, h1 = str(tmp_path / "w2.npz"), str(tmp_path / "w1.npz")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
@@ -250,7 +250,7 @@ def test_bench_rccl_branch_under_torchrun(tmp_path, gpu_lib):
                         "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port",
                         str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "1",
                         "--backend", "nccl", "--config", "c3", "--chains", "8192", "--steps", "2",
-                        "--warmup", "1", "--inner", "300", "--no-cpu-baseline",
+                        "--warmup", "1", "--inner", "300", "--full", "--no-cpu-baseline",
                         "--check-chains", "4"],
                        capture_output=True, text=True, timeout=400, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
