@@ -19,6 +19,7 @@ FW_EINVAL, FW_EHIP, FW_ESTATE, FW_EUNSUPPORTED, FW_ENOMEM = -1, -2, -3, -4, -5
 PROPOSE_BI, PROPOSE_PAIRS, PROPOSE_CUTEDGE = 0, 1, 2
 READ_LABELS, READ_STATS, READ_HIST_CUT, READ_HIST_B, READ_POPS = 0, 1, 2, 3, 4
 READ_HIST_RING, READ_RING_PAIR, READ_WAITS = 5, 6, 7
+READ_RUNG, READ_RUNG_STATS = 8, 9
 MAP_CUT_TIMES, MAP_NUM_FLIPS, MAP_PART_SUM, MAP_LAST_FLIPPED = 0, 1, 2, 3
 MAP_SUM, MAP_FINALIZE = 1, 2
 ACCEPT_CUT, ACCEPT_BRATIO, ACCEPT_BOUNDARY = 0, 1, 2
@@ -44,6 +45,20 @@ STATS_DTYPE = np.dtype(
         ("bnodes", "<i4"),
         ("npairs", "<i4"),
         ("stuck", "<i4"),
+    ]
+)
+
+# fw_rung_stats: per-rung observables of a replica set (fw_chains_set_ladder)
+RUNG_STATS_DTYPE = np.dtype(
+    [
+        ("yields", "<u8"),
+        ("steps", "<u8"),
+        ("accepts", "<u8"),
+        ("sum_cut", "<i8"),
+        ("sum_bnodes", "<i8"),
+        ("sum_invb", "<f8"),
+        ("swap_tried", "<u8"),
+        ("swap_done", "<u8"),
     ]
 )
 
@@ -75,6 +90,8 @@ SIGNATURES = [
     ("fw_chains_enable_maps", ctypes.c_int, [_P, _P]),
     ("fw_chains_enable_ring", ctypes.c_int, [_P, _P, _P, _I32]),
     ("fw_chains_enable_waits", ctypes.c_int, [_P, _P]),
+    ("fw_chains_set_ladder", ctypes.c_int, [_P, _P, _P, _I32, _P, _P]),
+    ("fw_chains_exchange_async", ctypes.c_int, [_P, _I64]),
     ("fw_chains_read_map", ctypes.c_int, [_P, _I32, _I32, _I32, _I32, _P, ctypes.c_size_t]),
     ("fw_eval_flips", ctypes.c_int,
      [_P, _P, _I32, _P, _P, _I32, _I64, _I64, _P, _P, _P, _P]),

@@ -86,6 +86,39 @@ def schedule_rows(base: float, beta_of_t, t_start: int, t_stop: int,
 ACCEPT_RULES = {"cut": _lib.ACCEPT_CUT, "bratio": _lib.ACCEPT_BRATIO,
                 "boundary": _lib.ACCEPT_BOUNDARY}
 
+MAX_RUNGS = 64  # one wave per replica set, one lane per rung (fw_chains_exchange_async)
+
+
+def ladder_layout(n_chains: int, n_rungs: int):
+    """The default placement of ``Chains.set_ladder``: consecutive chains form a replica
+    set, (set_of_chain, rung_of_chain) = (c // n_rungs, c % n_rungs)."""
+    c = np.arange(int(n_chains), dtype=np.int32)
+    return c // np.int32(n_rungs), c % np.int32(n_rungs)
+
+
+def check_ladder_layout(n_chains: int, n_rungs: int, set_of_chain, rung_of_chain):
+    """fw_chains_set_ladder's host validation (ValueError instead of FW_EINVAL): 2 <= n_rungs
+    <= 64 divides n_chains, set ids lie in [0, n_chains / n_rungs) and every (set, rung)
+    holds exactly one chain.  Returns the two arrays as contiguous int32."""
+    n_chains, n_rungs = int(n_chains), int(n_rungs)
+    if not 2 <= n_rungs <= MAX_RUNGS:
+        raise ValueError(f"n_rungs = {n_rungs} outside [2, {MAX_RUNGS}]")
+    if n_chains % n_rungs:
+        raise ValueError(f"{n_chains} chains are not a multiple of {n_rungs} rungs")
+    s = np.ascontiguousarray(set_of_chain, np.int32)
+    r = np.ascontiguousarray(rung_of_chain, np.int32)
+    if s.shape != (n_chains,) or r.shape != (n_chains,):
+        raise ValueError(f"set_of_chain and rung_of_chain must be [{n_chains}]")
+    n_sets = n_chains // n_rungs
+    if (s < 0).any() or (s >= n_sets).any() or (r < 0).any() or (r >= n_rungs).any():
+        raise ValueError(f"(set, rung) outside [0, {n_sets}) x [0, {n_rungs})")
+    count = np.bincount(s.astype(np.int64) * n_rungs + r, minlength=n_chains)
+    if (count != 1).any():
+        slot = int(np.flatnonzero(count != 1)[0])
+        raise ValueError(f"rung {slot % n_rungs} of set {slot // n_rungs} holds "
+                         f"{int(count[slot])} chains: every (set, rung) needs exactly one")
+    return s, r
+
 
 def expected_wait_sum(stats, n_nodes: int, k: int) -> np.ndarray:
     """Σ_t E[geom_wait_t] = (N^k - 1) * Σ 1/|B_t| - T (geom_wait, grid_chain_sec11.py:147-148)."""
@@ -124,6 +157,9 @@ class DeviceGraph:
         check(L.fw_graph_create(ptr(rowptr), ptr(col), ptr(pop), graph.n, len(col), device,
                                 _lib.ctypes.byref(h)))
         self._h = h
+        # handles of the chains created on this graph and not yet closed: fw_chains keeps a
+        # pointer to its fw_graph, so they must be destroyed before it (close)
+        self._live = {}
         info = np.zeros(5, np.int64)
         check(L.fw_graph_info(self._h, ptr(info)))
         self.n, self.n_edges, self.maxdeg, self.grid_w, self.grid_h = (int(x) for x in info)
@@ -134,6 +170,13 @@ class DeviceGraph:
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
+            # the garbage collector may finalise a graph before its chains: destroy them
+            # first (their Chains objects see the cleared handle and do nothing more)
+            for h in list(self._live.values()):
+                if h.value:
+                    _lib.load().fw_chains_destroy(h)
+                    h.value = None
+            self._live.clear()
             _lib.load().fw_graph_destroy(self._h)
             self._h = None
 
@@ -187,11 +230,13 @@ class Chains:
         self.accept_rule, self.node_flags = _lib.ACCEPT_CUT, None
         self._sched, self._sched_t0 = None, 0
         self.waits_on = False
+        self.ladder_bases, self.set_of_chain, self.ladder_round = None, None, 0
         h = _lib.ctypes.c_void_p()
         check(L.fw_chains_create(dgraph.handle, self.n_chains, self.k, ptr(lab), per_chain,
                                  self.mode, self.pop_lo, self.pop_hi, ptr(self.thr), thr_per,
                                  self.seed & (2**64 - 1), self.chain_id0, _lib.ctypes.byref(h)))
         self._h = h
+        dgraph._live[id(h)] = h
 
     # ------------------------------------------------------------- stepping
     def run(self, steps: int, max_retries: int = DEFAULT_MAX_RETRIES) -> None:
@@ -273,6 +318,63 @@ class Chains:
         check(_lib.load().fw_chains_set_schedule(self._h, ptr(r), r.shape[0], int(t0)))
         self._sched, self._sched_t0 = r, int(t0)
 
+    # ------------------------------------------------------------- replica exchange
+    def set_ladder(self, bases, set_of_chain=None, rung_of_chain=None) -> None:
+        """Join the chains into replica sets over a ladder of Metropolis bases
+        (fw_chains_set_ladder): rung r runs cut_accept with ``bases[r]``, and ``exchange``
+        lets neighbouring rungs of a set trade places.  The default placement is
+        ``ladder_layout``.  Needs the "cut" accept rule and no schedule.  Zeroes the rung
+        stats and restarts ``ladder_round``."""
+        bases = np.array(bases, np.float64).ravel()
+        if (set_of_chain is None) != (rung_of_chain is None):
+            raise ValueError("give both set_of_chain and rung_of_chain, or neither")
+        if set_of_chain is None:
+            set_of_chain, rung_of_chain = ladder_layout(self.n_chains, max(len(bases), 1))
+        s, r = check_ladder_layout(self.n_chains, len(bases), set_of_chain, rung_of_chain)
+        rows = np.ascontiguousarray(
+            np.stack([metropolis_table(float(b), self.dgraph.maxdeg) for b in bases]))
+        logb = np.array([math.log(float(b)) for b in bases], np.float64)
+        check(_lib.load().fw_chains_set_ladder(self._h, ptr(rows), ptr(logb), len(bases),
+                                               ptr(s), ptr(r)))
+        self.ladder_bases, self.set_of_chain, self.ladder_round = bases, s, 0
+
+    @property
+    def n_rungs(self) -> int:
+        return 0 if self.ladder_bases is None else len(self.ladder_bases)
+
+    def exchange(self, round: int) -> None:
+        """One exchange step on the handle's stream (fw_chains_exchange_async): pairs
+        (r, r+1) with r = round (mod 2) swap with probability min(1, (b_r / b_{r+1}) **
+        (cut_r - cut_{r+1})).  The draw is a function of (seed, round, set, r)."""
+        check(_lib.load().fw_chains_exchange_async(self._h, int(round)))
+
+    def rungs(self) -> np.ndarray:
+        """int32 [n_chains]: the rung each chain sits on now."""
+        return self._read(_lib.READ_RUNG, np.empty(self.n_chains, np.int32))
+
+    def rung_stats(self) -> np.ndarray:
+        """RUNG_STATS_DTYPE [n_sets, n_rungs]: yields, steps, accepts and the cut / boundary
+        sums of whichever chains sat on the rung, as of the last exchange, and the swaps
+        tried / done with the rung above."""
+        return self._read(_lib.READ_RUNG_STATS,
+                          np.empty((self.n_chains // self.n_rungs, self.n_rungs),
+                                   _lib.RUNG_STATS_DTYPE))
+
+    def run_tempered(self, steps_per_round: int, n_rounds: int, round0: Optional[int] = None,
+                     max_retries: int = DEFAULT_MAX_RETRIES) -> None:
+        """``n_rounds`` x (``steps_per_round`` steps, one exchange), enqueued back to back and
+        waited for once.  Rounds are numbered from ``round0`` (default: where the last call
+        stopped, ``ladder_round``), which fixes the parity and the draws of each exchange."""
+        if self.ladder_bases is None:
+            raise ValueError("run_tempered needs a ladder (set_ladder)")
+        r0 = self.ladder_round if round0 is None else int(round0)
+        L = _lib.load()
+        for i in range(int(n_rounds)):
+            check(L.fw_chains_run_async(self._h, int(steps_per_round), int(max_retries)))
+            check(L.fw_chains_exchange_async(self._h, r0 + i))
+        self.sync()
+        self.ladder_round = r0 + int(n_rounds)
+
     # ------------------------------------------------------------- sampled waits
     def enable_sampled_waits(self) -> None:
         """Draw geom_wait per state object (grid_chain_sec11.py:147-148, cached and re-used
@@ -326,7 +428,9 @@ class Chains:
     # ------------------------------------------------------------- checkpoint / resume
     def checkpoint(self) -> dict:
         """Everything a resumed chain needs: plans, the stats records (with the Philox
-        attempt counter: the counter-based RNG makes resume exact) and the histograms."""
+        attempt counter: the counter-based RNG makes resume exact) and the histograms; with
+        a ladder set, also its bases, the placement, every chain's rung, the rung stats and
+        the next round number."""
         ck = {"labels": self.labels(), "stats": self.stats(), "hist_cut": self.hist_cut(),
               "hist_b": self.hist_b(), "seed": np.uint64(self.seed),
               "chain_id0": np.int64(self.chain_id0), "thr": self.thr,
@@ -341,6 +445,10 @@ class Chains:
         if getattr(self, "ring", None) is not None:
             ck["hist_ring"] = self.hist_ring()
             ck["ring_u"], ck["ring_w"] = self.ring
+        if self.ladder_bases is not None:
+            ck["ladder_bases"], ck["set_of_chain"] = self.ladder_bases, self.set_of_chain
+            ck["rung"], ck["rung_stats"] = self.rungs(), self.rung_stats()
+            ck["ladder_round"] = np.int64(self.ladder_round)
         return ck
 
     def restore(self, ck: dict) -> None:
@@ -392,10 +500,21 @@ class Chains:
             self.set_schedule(ck["sched_rows"], int(ck["sched_t0"]))
         elif "accept_rule" in ck:
             self.set_schedule(None)
+        # the ladder last: it snapshots the stats records written above, and every chain
+        # takes the bounds of the rung it had reached
+        if "ladder_bases" in ck:
+            self.set_ladder(ck["ladder_bases"], ck["set_of_chain"], ck["rung"])
+            a = np.ascontiguousarray(ck["rung_stats"])
+            if a.nbytes != self.n_chains * _lib.RUNG_STATS_DTYPE.itemsize:
+                raise ValueError("checkpoint of another ladder shape")
+            check(L.fw_chains_write(self._h, _lib.READ_RUNG_STATS, ptr(a), a.nbytes))
+            self.ladder_round = int(ck["ladder_round"])
 
     def save_checkpoint(self, path: str) -> None:
         ck = self.checkpoint()
         ck["stats"] = ck["stats"].view(np.uint8)  # plain bytes: loadable without pickle
+        if "rung_stats" in ck:
+            ck["rung_stats"] = ck["rung_stats"].view(np.uint8)
         np.savez(path, **ck)
 
     @classmethod
@@ -449,9 +568,12 @@ class Chains:
         return out
 
     def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            _lib.load().fw_chains_destroy(self._h)
-            self._h = None
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            _lib.load().fw_chains_destroy(h)
+            h.value = None  # the handle object is shared with DeviceGraph._live
+            self.dgraph._live.pop(id(h), None)
+        self._h = None
 
     def __del__(self):
         try:

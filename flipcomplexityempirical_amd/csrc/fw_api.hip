@@ -177,6 +177,16 @@ struct fw_chains {
   int32_t* d_ring = nullptr;              // [2][ring_n] endpoints
   uint8_t* d_ring_node = nullptr;         // [n]
   unsigned long long* d_hist_ring = nullptr;  // [ring_n^2 + 1]
+  // fw_chains_set_ladder (n_rungs == 0: no ladder); FwExchangeParams names the arrays
+  int32_t n_rungs = 0;
+  double* d_lad_thr = nullptr;
+  uint64_t* d_lad_thr53 = nullptr;
+  double* d_logb = nullptr;
+  int32_t* d_rung = nullptr;
+  int32_t* d_chain_of = nullptr;
+  int64_t* d_gmin = nullptr;
+  FwRungSnap* d_snap = nullptr;
+  fw_rung_stats* d_rstats = nullptr;
 };
 
 namespace {
@@ -276,6 +286,16 @@ void ring_pair_of(const fw_chains* c, const int16_t* lab, int32_t* out) {
   for (int r = 0; r < c->ring_n && found < 2; ++r)
     if (lab[c->ring_u[r]] != lab[c->ring_w[r]]) out[found++] = r;
   if (found < 2) out[0] = out[1] = -1;
+}
+
+// the rung stats' snapshot := the stats records st [n_chains] (fw_chains_set_ladder)
+int ladder_snapshot(fw_chains* c, const fw_chain_stats* st) {
+  std::vector<FwRungSnap> sn((size_t)c->n_chains);
+  for (int i = 0; i < c->n_chains; ++i)
+    sn[i] = FwRungSnap{st[i].yields, st[i].steps, st[i].accepts,
+                       st[i].sum_cut, st[i].sum_bnodes, st[i].sum_invb};
+  HIPCHK(hipMemcpy(c->d_snap, sn.data(), sizeof(FwRungSnap) * sn.size(), hipMemcpyHostToDevice));
+  return FW_OK;
 }
 
 }  // namespace
@@ -470,7 +490,8 @@ void fw_chains_destroy(fw_chains* c) {
                   c->d_spill,  c->d_next,  c->d_acc,  c->d_nf,   c->d_lf,       c->d_ps,
                   c->d_pend,   c->d_labval, c->d_flags, c->d_bcnt, c->d_sched, c->d_sched53,
                   c->d_ring,   c->d_ring_node, c->d_hist_ring, c->d_gscr, c->d_segdone,
-                  c->d_wsamp,  c->d_wlp};
+                  c->d_wsamp,  c->d_wlp,   c->d_lad_thr, c->d_lad_thr53, c->d_logb, c->d_rung,
+                  c->d_chain_of, c->d_gmin, c->d_snap, c->d_rstats};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -928,6 +949,18 @@ int fw_chains_read(fw_chains* c, int32_t what, void* host_dst, size_t bytes) {
       if (bytes < need) return fail(FW_EINVAL, "waits need %zu bytes", need);
       HIPCHK(hipMemcpy(host_dst, c->d_wsamp, need, hipMemcpyDeviceToHost));
       return FW_OK;
+    case FW_READ_RUNG:
+      if (!c->n_rungs) return fail(FW_ESTATE, "no ladder is set");
+      need = sizeof(int32_t) * (size_t)c->n_chains;
+      if (bytes < need) return fail(FW_EINVAL, "rungs need %zu bytes", need);
+      HIPCHK(hipMemcpy(host_dst, c->d_rung, need, hipMemcpyDeviceToHost));
+      return FW_OK;
+    case FW_READ_RUNG_STATS:
+      if (!c->n_rungs) return fail(FW_ESTATE, "no ladder is set");
+      need = sizeof(fw_rung_stats) * (size_t)c->n_chains;  // n_sets * n_rungs
+      if (bytes < need) return fail(FW_EINVAL, "rung stats need %zu bytes", need);
+      HIPCHK(hipMemcpy(host_dst, c->d_rstats, need, hipMemcpyDeviceToHost));
+      return FW_OK;
     default:
       return fail(FW_EINVAL, "unknown read kind %d", what);
   }
@@ -982,6 +1015,8 @@ int fw_chains_write(fw_chains* c, int32_t what, const void* host_src, size_t byt
         for (int i = 0; i < c->n_chains; ++i) ymax = std::max<uint64_t>(ymax, st[i].yields);
         c->max_yields = ymax;
       }
+      // a ladder's rung stats count from the written records on
+      if (c->n_rungs) return ladder_snapshot(c, static_cast<const fw_chain_stats*>(host_src));
       return FW_OK;
     case FW_READ_HIST_CUT:
       need = sizeof(uint64_t) * (c->g->nnz / 2 + 1);
@@ -1005,6 +1040,12 @@ int fw_chains_write(fw_chains* c, int32_t what, const void* host_src, size_t byt
       if (bytes < need) return fail(FW_EINVAL, "waits need %zu bytes", need);
       HIPCHK(hipMemcpy(c->d_wsamp, host_src, need, hipMemcpyHostToDevice));
       return FW_OK;
+    case FW_READ_RUNG_STATS:
+      if (!c->n_rungs) return fail(FW_ESTATE, "no ladder is set");
+      need = sizeof(fw_rung_stats) * (size_t)c->n_chains;
+      if (bytes < need) return fail(FW_EINVAL, "rung stats need %zu bytes", need);
+      HIPCHK(hipMemcpy(c->d_rstats, host_src, need, hipMemcpyHostToDevice));
+      return FW_OK;
     default:
       return fail(FW_EINVAL, "fw_chains_write: unsupported kind %d", what);
   }
@@ -1025,6 +1066,10 @@ int fw_chains_reset_observables(fw_chains* c) {
   }
   HIPCHK(hipMemcpy(c->d_stats, st.data(), sizeof(fw_chain_stats) * st.size(),
                    hipMemcpyHostToDevice));
+  if (c->n_rungs) {  // the rung stats restart with the sums
+    HIPCHK(hipMemset(c->d_rstats, 0, sizeof(fw_rung_stats) * (size_t)c->n_chains));
+    if (const int rc = ladder_snapshot(c, st.data())) return rc;
+  }
   HIPCHK(hipMemset(c->d_hist_cut, 0,
                    sizeof(unsigned long long) * (c->g->nnz / 2 + 1 + FW_HIST_PAD)));
   HIPCHK(hipMemset(c->d_hist_b, 0, sizeof(unsigned long long) * (c->g->n + 1 + FW_HIST_PAD)));
@@ -1047,6 +1092,8 @@ int fw_chains_set_accept(fw_chains* c, int32_t rule, const uint8_t* node_flags) 
   if (!c) return fail(FW_EINVAL, "null handle");
   if (rule < FW_ACCEPT_CUT || rule > FW_ACCEPT_BOUNDARY)
     return fail(FW_EINVAL, "unknown accept rule %d", rule);
+  if (c->n_rungs && rule != FW_ACCEPT_CUT)
+    return fail(FW_EUNSUPPORTED, "a base ladder exchanges under FW_ACCEPT_CUT only");
   HIPCHK(hipSetDevice(c->g->device));
   HIPCHK(hipStreamSynchronize(c->stream));
   if (rule == FW_ACCEPT_BOUNDARY) {
@@ -1076,6 +1123,8 @@ int fw_chains_set_accept(fw_chains* c, int32_t rule, const uint8_t* node_flags) 
 int fw_chains_set_schedule(fw_chains* c, const double* rows, int32_t n_rows, int64_t t0) {
   if (!c) return fail(FW_EINVAL, "null handle");
   if (n_rows < 0 || (n_rows > 0 && !rows)) return fail(FW_EINVAL, "bad schedule rows");
+  if (c->n_rungs && n_rows > 0)
+    return fail(FW_EUNSUPPORTED, "a base ladder exchanges without a bound schedule only");
   HIPCHK(hipSetDevice(c->g->device));
   HIPCHK(hipStreamSynchronize(c->stream));
   if (c->d_sched) (void)hipFree(c->d_sched);
@@ -1169,6 +1218,130 @@ int fw_chains_enable_waits(fw_chains* c, const double* p_table) {
   HIPCHK(hipMemset(c->d_wsamp, 0, sizeof(double) * 2 * (size_t)c->n_chains));
   c->p.wsamp = c->d_wsamp;
   c->p.wlp = c->d_wlp;
+  return FW_OK;
+}
+
+int fw_chains_set_ladder(fw_chains* c, const double* thr_rows, const double* log_base,
+                         int32_t n_rungs, const int32_t* set_of_chain,
+                         const int32_t* rung_of_chain) {
+  if (!c || !thr_rows || !log_base || !set_of_chain || !rung_of_chain)
+    return fail(FW_EINVAL, "fw_chains_set_ladder: null");
+  if (n_rungs < 2 || n_rungs > 64) return fail(FW_EINVAL, "n_rungs = %d outside [2, 64]", n_rungs);
+  const int C = c->n_chains;
+  if (C % n_rungs)
+    return fail(FW_EINVAL, "%d chains are not a multiple of %d rungs", C, n_rungs);
+  const int n_sets = C / n_rungs;
+  // C chains over C (set, rung) slots, none twice: every slot exactly once
+  std::vector<int32_t> chain_of((size_t)C, -1);
+  std::vector<int64_t> gmin((size_t)n_sets, -1);
+  for (int i = 0; i < C; ++i) {
+    const int s = set_of_chain[i], r = rung_of_chain[i];
+    if (s < 0 || s >= n_sets || r < 0 || r >= n_rungs)
+      return fail(FW_EINVAL, "chain %d: (set %d, rung %d) outside [0, %d) x [0, %d)", i, s, r,
+                  n_sets, n_rungs);
+    int32_t& slot = chain_of[(size_t)s * n_rungs + r];
+    if (slot >= 0)
+      return fail(FW_EINVAL, "chains %d and %d both sit on rung %d of set %d", slot, i, r, s);
+    slot = i;
+    if (gmin[s] < 0) gmin[s] = c->p.chain_id0 + i;  // ascending i: the set's smallest id
+  }
+  if (c->p.accept != FW_ACCEPT_CUT || c->p.sched != nullptr)
+    return fail(FW_EUNSUPPORTED,
+                "a base ladder exchanges under FW_ACCEPT_CUT without a bound schedule only");
+  HIPCHK(hipSetDevice(c->g->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const size_t L = (size_t)(2 * c->D + 1);
+  std::vector<uint64_t> lad53((size_t)n_rungs * L);
+  for (size_t i = 0; i < lad53.size(); ++i) lad53[i] = thr53_of(thr_rows[i]);
+  std::vector<double> thr((size_t)C * L);
+  std::vector<uint64_t> thr53((size_t)C * L);
+  for (int i = 0; i < C; ++i) {
+    std::memcpy(&thr[(size_t)i * L], thr_rows + (size_t)rung_of_chain[i] * L, sizeof(double) * L);
+    std::memcpy(&thr53[(size_t)i * L], &lad53[(size_t)rung_of_chain[i] * L], sizeof(uint64_t) * L);
+  }
+  std::vector<fw_chain_stats> st((size_t)C);
+  HIPCHK(hipMemcpy(st.data(), c->d_stats, sizeof(fw_chain_stats) * st.size(),
+                   hipMemcpyDeviceToHost));
+  // the new buffers first: on failure the handle keeps what it had.  A handle created with
+  // one shared table gets per-chain tables (slots 8, 9).
+  const bool shared = c->p.thr_stride == 0;
+  void* nb[10] = {};
+  const size_t sz[10] = {sizeof(double) * n_rungs * L,    sizeof(uint64_t) * n_rungs * L,
+                         sizeof(double) * n_rungs,        sizeof(int32_t) * C,
+                         sizeof(int32_t) * C,             sizeof(int64_t) * n_sets,
+                         sizeof(FwRungSnap) * C,          sizeof(fw_rung_stats) * C,
+                         shared ? sizeof(double) * C * L : 0, shared ? sizeof(uint64_t) * C * L : 0};
+  bool ok = true;
+  for (int i = 0; i < 10 && ok; ++i) ok = sz[i] == 0 || hipMalloc(&nb[i], sz[i]) == hipSuccess;
+  void* d_thr = shared ? nb[8] : (void*)c->d_thr;
+  void* d_thr53 = shared ? nb[9] : (void*)c->d_thr53;
+  const bool up =
+      ok && hipMemcpy(nb[0], thr_rows, sz[0], hipMemcpyHostToDevice) == hipSuccess &&
+      hipMemcpy(nb[1], lad53.data(), sz[1], hipMemcpyHostToDevice) == hipSuccess &&
+      hipMemcpy(nb[2], log_base, sz[2], hipMemcpyHostToDevice) == hipSuccess &&
+      hipMemcpy(nb[3], rung_of_chain, sz[3], hipMemcpyHostToDevice) == hipSuccess &&
+      hipMemcpy(nb[4], chain_of.data(), sz[4], hipMemcpyHostToDevice) == hipSuccess &&
+      hipMemcpy(nb[5], gmin.data(), sz[5], hipMemcpyHostToDevice) == hipSuccess &&
+      hipMemset(nb[7], 0, sz[7]) == hipSuccess &&
+      hipMemcpy(d_thr, thr.data(), sizeof(double) * C * L, hipMemcpyHostToDevice) == hipSuccess &&
+      hipMemcpy(d_thr53, thr53.data(), sizeof(uint64_t) * C * L, hipMemcpyHostToDevice) ==
+          hipSuccess;
+  if (!up) {
+    for (void* b : nb)
+      if (b) (void)hipFree(b);
+    return ok ? fail(FW_EHIP, "ladder upload failed")
+              : fail(FW_ENOMEM, "ladder of %d rungs for %d chains", n_rungs, C);
+  }
+  void* old[] = {c->d_lad_thr, c->d_lad_thr53, c->d_logb, c->d_rung,
+                 c->d_chain_of, c->d_gmin,     c->d_snap, c->d_rstats,
+                 shared ? (void*)c->d_thr : nullptr, shared ? (void*)c->d_thr53 : nullptr};
+  for (void* b : old)
+    if (b) (void)hipFree(b);
+  c->d_lad_thr = static_cast<double*>(nb[0]);
+  c->d_lad_thr53 = static_cast<uint64_t*>(nb[1]);
+  c->d_logb = static_cast<double*>(nb[2]);
+  c->d_rung = static_cast<int32_t*>(nb[3]);
+  c->d_chain_of = static_cast<int32_t*>(nb[4]);
+  c->d_gmin = static_cast<int64_t*>(nb[5]);
+  c->d_snap = static_cast<FwRungSnap*>(nb[6]);
+  c->d_rstats = static_cast<fw_rung_stats*>(nb[7]);
+  c->d_thr = static_cast<double*>(d_thr);
+  c->d_thr53 = static_cast<uint64_t*>(d_thr53);
+  c->p.thr = c->d_thr;
+  c->p.thr53 = c->d_thr53;
+  c->p.thr_stride = (int32_t)L;
+  c->n_rungs = n_rungs;
+  return ladder_snapshot(c, st.data());
+}
+
+int fw_chains_exchange_async(fw_chains* c, int64_t round) {
+  if (!c) return fail(FW_EINVAL, "null handle");
+  if (!c->n_rungs) return fail(FW_EINVAL, "fw_chains_exchange_async: no ladder is set");
+  if (round < 0 || round > 0xFFFFFFFFll)
+    return fail(FW_EINVAL, "round %lld outside [0, 2^32)", (long long)round);
+  HIPCHK(hipSetDevice(c->g->device));
+  FwExchangeParams e{};
+  e.stats = c->d_stats;
+  e.snap = c->d_snap;
+  e.rstats = c->d_rstats;
+  e.thr = c->d_thr;
+  e.thr53 = c->d_thr53;
+  e.lad_thr = c->d_lad_thr;
+  e.lad_thr53 = c->d_lad_thr53;
+  e.log_base = c->d_logb;
+  e.rung = c->d_rung;
+  e.chain_of = c->d_chain_of;
+  e.gmin = c->d_gmin;
+  e.n_sets = c->n_chains / c->n_rungs;
+  e.n_rungs = c->n_rungs;
+  e.row_len = 2 * c->D + 1;
+  e.round = (uint32_t)round;
+  e.seed = c->p.seed;
+  // plans, cut, bnodes and npairs stay with their chains: the derived-state cache and the
+  // run timing events are left alone
+  const int le = fw_launch_exchange(e, c->stream);
+  if (le != 0)
+    return fail(FW_EHIP, "exchange launch failed: %s", hipGetErrorString((hipError_t)le));
   return FW_OK;
 }
 

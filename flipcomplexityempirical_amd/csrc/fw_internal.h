@@ -163,7 +163,34 @@ struct FwEvalParams {
   int32_t off_list, lds_bytes;
 };
 
+// fw_chains_exchange_async: the fields of a stats record the rung stats accumulate, as of
+// the last exchange (or set_ladder / reset / stats write)
+struct FwRungSnap {
+  uint64_t yields, steps, accepts;
+  int64_t sum_cut, sum_bnodes;
+  double sum_invb;
+};
+
+// One replica-exchange step (see include/flipwalk.h); set s holds chains chain_of[s][0..n_rungs)
+struct FwExchangeParams {
+  const fw_chain_stats* stats;  // [n_chains]
+  FwRungSnap* snap;             // [n_chains]
+  fw_rung_stats* rstats;        // [n_sets][n_rungs]
+  double* thr;                  // [n_chains][row_len]: the run kernels' per-chain tables
+  uint64_t* thr53;
+  const double* lad_thr;        // [n_rungs][row_len]
+  const uint64_t* lad_thr53;
+  const double* log_base;       // [n_rungs]
+  int32_t* rung;                // [n_chains]
+  int32_t* chain_of;            // [n_sets][n_rungs]
+  const int64_t* gmin;          // [n_sets] smallest global chain id of the set
+  int32_t n_sets, n_rungs, row_len;
+  uint32_t round;
+  uint64_t seed;
+};
+
 // Host-side launchers implemented in fw_kernels.hip.
+int fw_launch_exchange(const FwExchangeParams& e, void* stream);
 int fw_launch_map_init(const FwRunParams& p, void* stream);
 int fw_launch_map_read(const FwMapRead& m, void* stream);
 int fw_launch_bcnt_init(const FwRunParams& p, void* stream);

@@ -865,3 +865,64 @@ int fw_launch_eval(const FwEvalParams& p, int lb, int grid, void* stream) {
   return (int)hipLaunchKernel(fn, dim3(grid), dim3(64), args, (size_t)p.lds_bytes,
                               (hipStream_t)stream);
 }
+
+// ---------------------------------------------------------------- replica exchange
+// One exchange step of a base ladder (fw_chains_exchange_async, include/flipwalk.h): one
+// wave per replica set, lane r owns the chain now on rung r.  A lane writes only its own
+// chain's records (snapshot, rung, thr row), its rung's stats and the rung -> chain slot its
+// chain moves to (the slots written are a permutation of the set's), and every lane has read
+// what it needs before the first shuffle returns: no atomics, no dependence on thread order.
+__global__ __launch_bounds__(64) void fw_exchange_kernel(FwExchangeParams e) {
+#pragma clang fp contract(off)
+  const int set = blockIdx.x, r = threadIdx.x;
+  const bool on = r < e.n_rungs;
+  const size_t slot = (size_t)set * e.n_rungs + (on ? r : 0);
+  const int ch = e.chain_of[slot];
+  const fw_chain_stats* st = e.stats + ch;
+  const int cut = st->cut, stuck = st->stuck;
+  fw_rung_stats rs = e.rstats[slot];
+  if (on) {  // accumulate what the chain did since its last snapshot, all of it on rung r
+    const FwRungSnap cur{st->yields, st->steps, st->accepts, st->sum_cut, st->sum_bnodes,
+                         st->sum_invb};
+    const FwRungSnap sn = e.snap[ch];
+    rs.yields += cur.yields - sn.yields;
+    rs.steps += cur.steps - sn.steps;
+    rs.accepts += cur.accepts - sn.accepts;
+    rs.sum_cut += cur.sum_cut - sn.sum_cut;
+    rs.sum_bnodes += cur.sum_bnodes - sn.sum_bnodes;
+    rs.sum_invb = rs.sum_invb + (cur.sum_invb - sn.sum_invb);
+    e.snap[ch] = cur;
+  }
+  const int cut_up = __shfl_down(cut, 1, WAVE), stuck_up = __shfl_down(stuck, 1, WAVE);
+  // lane r decides the pair (r, r+1)
+  const bool lead = on && ((((uint32_t)r ^ e.round) & 1u) == 0u) && r + 1 < e.n_rungs &&
+                    !stuck && !stuck_up;
+  bool swap = false;
+  if (lead) {
+    const double x = (double)(cut - cut_up) * (e.log_base[r] - e.log_base[r + 1]);
+    const uint64_t g = (uint64_t)e.gmin[set];
+    const U4 y = philox(e.round, 0x40000000u | (uint32_t)r, (uint32_t)g, (uint32_t)(g >> 32),
+                        (uint32_t)e.seed, (uint32_t)(e.seed >> 32));
+    swap = fw_log1p(-u53(y.x2, y.x3)) <= x;
+    rs.swap_tried += 1;
+    rs.swap_done += swap ? 1 : 0;
+  }
+  const bool down = __shfl_up((int)swap, 1, WAVE) != 0 && r > 0;  // pair (r-1, r) swapped
+  if (!on) return;
+  e.rstats[slot] = rs;
+  const int nr = r + (swap ? 1 : 0) - (down ? 1 : 0);
+  if (nr == r) return;
+  e.rung[ch] = nr;
+  e.chain_of[(size_t)set * e.n_rungs + nr] = ch;
+  const size_t dst = (size_t)ch * e.row_len, src = (size_t)nr * e.row_len;
+  for (int i = 0; i < e.row_len; ++i) {
+    e.thr[dst + i] = e.lad_thr[src + i];
+    e.thr53[dst + i] = e.lad_thr53[src + i];
+  }
+}
+
+int fw_launch_exchange(const FwExchangeParams& e, void* stream) {
+  void* args[] = {const_cast<FwExchangeParams*>(&e)};
+  return (int)hipLaunchKernel(reinterpret_cast<void*>(&fw_exchange_kernel), dim3(e.n_sets),
+                              dim3(64), args, 0, (hipStream_t)stream);
+}

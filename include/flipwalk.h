@@ -90,6 +90,8 @@ extern "C" {
 #define FW_READ_RING_PAIR 6 /* int32  [n_chains][2] current ring pair (i, j), -1 = none */
 #define FW_READ_WAITS 7    /* double [n_chains][2] {sum of sampled waits over yields, the
                               current state's draw} (fw_chains_enable_waits)             */
+#define FW_READ_RUNG 8        /* int32 [n_chains] current rung of each chain (read only)   */
+#define FW_READ_RUNG_STATS 9  /* fw_rung_stats [n_sets][n_rungs] (read and fw_chains_write) */
 
 /* ---- district-shape observable (fw_chains_enable_ring) ----------------------
  * boundary_slope (grid_chain_sec11.py:55-78; Frankenstein_chain.py:57-80) collects the
@@ -144,6 +146,15 @@ typedef struct fw_chain_stats {
   int32_t stuck;        /* 1 once max_retries consecutive proposals failed     */
 } fw_chain_stats;
 
+/* Per-rung observables of one replica set (fw_chains_set_ladder): what the chains did
+ * while they sat on the rung, whichever chain that was. */
+typedef struct fw_rung_stats {          /* 64 bytes */
+  uint64_t yields, steps, accepts;      /* summed over the launches a chain spent on the rung */
+  int64_t sum_cut, sum_bnodes;
+  double sum_invb;
+  uint64_t swap_tried, swap_done;       /* pair (r, r+1), kept at rung r */
+} fw_rung_stats;
+
 typedef struct fw_graph fw_graph;
 typedef struct fw_chains fw_chains;
 
@@ -152,7 +163,8 @@ const char* fw_last_error(void);
 
 /* Library/ABI version, e.g. 0x000600 for 0.6.0 (0.2: spatial maps; 0.3: bound
  * schedules; 0.4: ring observable, checkpoint/resume; 0.5: sampled geometric waits;
- * 0.6: fw_chains_launch_info; 0.7: fw_build_info). */
+ * 0.6: fw_chains_launch_info; 0.7: fw_build_info; the ladder entry points
+ * fw_chains_set_ladder / fw_chains_exchange_async arrived in 0.7 without a bump). */
 int32_t fw_version(void);
 
 /* Provenance of this build (static string, never NULL): "src=<sha256 of every kernel,
@@ -278,6 +290,51 @@ int fw_chains_enable_ring(fw_chains* c, const int32_t* ring_u, const int32_t* ri
  * operations, so every implementation agrees bit for bit).  Read / write with
  * FW_READ_WAITS.  The Rao-Blackwellised expectation (stats sum_invb) stays available. */
 int fw_chains_enable_waits(fw_chains* c, const double* p_table);
+
+/* Replica exchange (parallel tempering) across a ladder of Metropolis bases.  No reference
+ * counterpart: the reference sweeps its bases one run at a time; this joins
+ * the rungs of such a sweep into one sampler.  A replica set is n_rungs chains of the
+ * handle, one per rung; rung r runs under thr_rows[r] (thr[d + maxdeg] = base_r ** (-d))
+ * and log_base[r] = log(base_r).  set_of_chain / rung_of_chain [n_chains] place every chain.
+ *  - FW_EINVAL unless 2 <= n_rungs <= 64, n_chains % n_rungs == 0, set ids lie in
+ *    [0, n_chains / n_rungs) and every (set, rung) occurs exactly once (checked on the
+ *    host before the device is touched).
+ *  - FW_EUNSUPPORTED unless the accept rule is FW_ACCEPT_CUT and no schedule is set: only
+ *    then is the jump chain's stationary law f(x) * base ** (-cut(x)) with f free of the
+ *    base, so that the swap ratio below is exact for all three proposal modes.  On a
+ *    laddered handle fw_chains_set_accept with another rule and fw_chains_set_schedule
+ *    with rows fail with FW_EUNSUPPORTED.
+ * The call gives every chain the thr row of its rung (a handle created with one shared
+ * table gets per-chain tables), zeroes the rung stats and snapshots the stats records.
+ * It may be called again; that, followed by a FW_READ_RUNG_STATS write, restores a
+ * checkpoint.  fw_chains_reset_observables also zeroes the rung stats and re-snapshots;
+ * a FW_READ_STATS write re-snapshots.
+ *
+ * fw_chains_exchange_async (0 <= round < 2^32; FW_EINVAL without a ladder) enqueues one
+ * exchange step on the handle's stream, with no host synchronisation; it does not touch
+ * fw_chains_last_kernel_ms.  One wave per replica set, lane r owning the chain now on
+ * rung r; no atomics, no dependence on thread order:
+ *  1. Accumulate.  rung_stats[set][r] += (stats - snapshot) of the chain's yields, steps,
+ *     accepts, sum_cut and sum_bnodes; sum_invb = sum_invb + (cur - snap) in plain IEEE
+ *     double operations; then snapshot = stats.
+ *  2. Swap.  For each pair (r, r+1) with r = round (mod 2), r+1 < n_rungs and neither chain
+ *     stuck: d = cut(chain on r) - cut(chain on r+1) from the stats records,
+ *     x = (double)d * (log_base[r] - log_base[r+1]) (one subtraction, one multiplication);
+ *     the Philox4x32-10 block key = seed, ctr = (lo32(round), 2^30 | r, lo32(g), hi32(g)),
+ *     g = the smallest global chain id (chain_id0 + local index) in the set, gives
+ *     u = ((x2>>5)*2^26 + (x3>>6)) * 2^-53; the pair swaps iff log1p(-u) <= x (log1p as
+ *     for the sampled waits: plain IEEE double operations), i.e. with probability
+ *     min(1, (base_r / base_{r+1}) ** d).  swap_tried / swap_done count at rung r.  On a
+ *     swap the two chains trade rungs: FW_READ_RUNG and each chain's thr row change;
+ *     plans, counters and sums stay with the chain.
+ * Counter word 1 has bit 30 set and bit 31 clear: disjoint from the proposal draws (word 1
+ * = hi32(t) < 2^30) and from the wait draws (bit 31 set).  The run kernels are unchanged:
+ * they read a chain's thr row at the start of every launch.
+ * (These entry points arrived in 0.7 without a version bump.) */
+int fw_chains_set_ladder(fw_chains* c, const double* thr_rows /*[n_rungs][2*maxdeg+1]*/,
+                         const double* log_base /*[n_rungs]*/, int32_t n_rungs,
+                         const int32_t* set_of_chain, const int32_t* rung_of_chain);
+int fw_chains_exchange_async(fw_chains* c, int64_t round);
 
 /* Read a map (FW_MAP_*) of chains [chain0, chain0 + n_chains) as int64
  * [n_chains][len], or with FW_MAP_SUM its sum over those chains [len]; len is
