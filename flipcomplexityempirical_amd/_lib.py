@@ -23,6 +23,8 @@ READ_RUNG, READ_RUNG_STATS = 8, 9
 MAP_CUT_TIMES, MAP_NUM_FLIPS, MAP_PART_SUM, MAP_LAST_FLIPPED = 0, 1, 2, 3
 MAP_SUM, MAP_FINALIZE = 1, 2
 ACCEPT_CUT, ACCEPT_BRATIO, ACCEPT_BOUNDARY = 0, 1, 2
+SERIES_CUT, SERIES_BNODES, SERIES_RUNG, SERIES_BY_RUNG = 0, 1, 2, 4
+SERIES_MAX_LAG = 1023
 
 STATS_DTYPE = np.dtype(
     [
@@ -92,6 +94,13 @@ SIGNATURES = [
     ("fw_chains_enable_waits", ctypes.c_int, [_P, _P]),
     ("fw_chains_set_ladder", ctypes.c_int, [_P, _P, _P, _I32, _P, _P]),
     ("fw_chains_exchange_async", ctypes.c_int, [_P, _I64]),
+    ("fw_chains_enable_series", ctypes.c_int, [_P, _I64]),
+    ("fw_chains_record_async", ctypes.c_int, [_P]),
+    ("fw_chains_series_info", ctypes.c_int, [_P, _P]),
+    ("fw_chains_series_reset", ctypes.c_int, [_P]),
+    ("fw_chains_read_series", ctypes.c_int, [_P, _I32, _I64, _I64, _P, ctypes.c_size_t]),
+    ("fw_chains_write_series", ctypes.c_int, [_P, _I32, _I64, _I64, _P, ctypes.c_size_t]),
+    ("fw_chains_series_acf", ctypes.c_int, [_P, _I32, _I64, _I64, _I32, _P, _P]),
     ("fw_chains_read_map", ctypes.c_int, [_P, _I32, _I32, _I32, _I32, _P, ctypes.c_size_t]),
     ("fw_eval_flips", ctypes.c_int,
      [_P, _P, _I32, _P, _P, _I32, _I64, _I64, _P, _P, _P, _P]),

@@ -88,6 +88,8 @@ ACCEPT_RULES = {"cut": _lib.ACCEPT_CUT, "bratio": _lib.ACCEPT_BRATIO,
 
 MAX_RUNGS = 64  # one wave per replica set, one lane per rung (fw_chains_exchange_async)
 
+SERIES_KINDS = {"cut": _lib.SERIES_CUT, "bnodes": _lib.SERIES_BNODES, "rung": _lib.SERIES_RUNG}
+
 
 def ladder_layout(n_chains: int, n_rungs: int):
     """The default placement of ``Chains.set_ladder``: consecutive chains form a replica
@@ -231,6 +233,9 @@ class Chains:
         self._sched, self._sched_t0 = None, 0
         self.waits_on = False
         self.ladder_bases, self.set_of_chain, self.ladder_round = None, None, 0
+        # enable_series: the capacity and, per sample, the ladder epoch of its rung row (a
+        # mirror of the handle's stamps, which a checkpoint carries as a validity mask)
+        self.series_capacity, self._series_epoch = 0, None
         h = _lib.ctypes.c_void_p()
         check(L.fw_chains_create(dgraph.handle, self.n_chains, self.k, ptr(lab), per_chain,
                                  self.mode, self.pop_lo, self.pop_hi, ptr(self.thr), thr_per,
@@ -361,19 +366,112 @@ class Chains:
                                    _lib.RUNG_STATS_DTYPE))
 
     def run_tempered(self, steps_per_round: int, n_rounds: int, round0: Optional[int] = None,
-                     max_retries: int = DEFAULT_MAX_RETRIES) -> None:
+                     max_retries: int = DEFAULT_MAX_RETRIES, record: bool = False) -> None:
         """``n_rounds`` x (``steps_per_round`` steps, one exchange), enqueued back to back and
         waited for once.  Rounds are numbered from ``round0`` (default: where the last call
-        stopped, ``ladder_round``), which fixes the parity and the draws of each exchange."""
+        stopped, ``ladder_round``), which fixes the parity and the draws of each exchange.
+        With ``record`` every round is run, record, exchange: a series sample carries the rung
+        its chain has just run on."""
         if self.ladder_bases is None:
             raise ValueError("run_tempered needs a ladder (set_ladder)")
         r0 = self.ladder_round if round0 is None else int(round0)
         L = _lib.load()
         for i in range(int(n_rounds)):
             check(L.fw_chains_run_async(self._h, int(steps_per_round), int(max_retries)))
+            if record:
+                self.record()
             check(L.fw_chains_exchange_async(self._h, r0 + i))
         self.sync()
         self.ladder_round = r0 + int(n_rounds)
+
+    # ------------------------------------------------------------- observable series
+    def enable_series(self, capacity: int) -> None:
+        """Keep up to ``capacity`` thinned samples of every chain's cut and boundary size
+        (and rung, under a ladder) on the device (fw_chains_enable_series); once per handle."""
+        check(_lib.load().fw_chains_enable_series(self._h, int(capacity)))
+        self.series_capacity = int(capacity)
+        self._series_epoch = np.zeros(int(capacity), np.int64)
+
+    def series_info(self) -> dict:
+        info = np.zeros(4, np.int64)
+        check(_lib.load().fw_chains_series_info(self._h, ptr(info)))
+        return {"capacity": int(info[0]), "n_samples": int(info[1]), "epoch": int(info[2]),
+                "n_rungs": int(info[3])}
+
+    @property
+    def n_samples(self) -> int:
+        return self.series_info()["n_samples"]
+
+    def record(self) -> None:
+        """One sample of every chain, enqueued on the handle's stream behind the runs already
+        there (fw_chains_record_async); no wait."""
+        check(_lib.load().fw_chains_record_async(self._h))
+        info = self.series_info()
+        self._series_epoch[info["n_samples"] - 1] = info["epoch"]
+
+    def series_reset(self) -> None:
+        check(_lib.load().fw_chains_series_reset(self._h))
+
+    def _series_window(self, t0, n):
+        t0 = int(t0)
+        return t0, (self.n_samples - t0 if n is None else int(n))
+
+    def series(self, what: str | int, by_rung: bool = False, t0: int = 0,
+               n: Optional[int] = None) -> np.ndarray:
+        """int32 [n, n_chains]: samples t0 .. t0 + n - 1 (default: to the last) of "cut",
+        "bnodes" or "rung", one column per chain; with ``by_rung`` one column per
+        (set, rung) slot, set * n_rungs + rung, holding the chain that sat there."""
+        kind = SERIES_KINDS[what] if isinstance(what, str) else int(what)
+        t0, n = self._series_window(t0, n)
+        out = np.empty((max(n, 0), self.n_chains), np.int32)
+        if n == 0:
+            return out
+        check(_lib.load().fw_chains_read_series(
+            self._h, kind | (_lib.SERIES_BY_RUNG if by_rung else 0), t0, n, ptr(out), out.nbytes))
+        return out
+
+    def write_series(self, what: str | int, values, t0: int = 0) -> None:
+        """Overwrite samples t0 .. of a series from int32 [n, n_chains] (checkpoints, tests);
+        see fw_chains_write_series for what is validated."""
+        kind = SERIES_KINDS[what] if isinstance(what, str) else int(what)
+        a = np.ascontiguousarray(values, np.int32)
+        if a.ndim != 2 or a.shape[1] != self.n_chains:
+            raise ValueError(f"series values must be [n, {self.n_chains}]")
+        before = self.n_samples if self.series_capacity else 0
+        check(_lib.load().fw_chains_write_series(self._h, kind, int(t0), a.shape[0], ptr(a),
+                                                 a.nbytes))
+        lo, hi = int(t0), int(t0) + a.shape[0]
+        if kind == _lib.SERIES_RUNG:
+            self._series_epoch[lo:hi] = self.series_info()["epoch"]
+        elif hi > before:
+            self._series_epoch[before:hi] = 0
+
+    def series_acf(self, what: str | int, max_lag: int, by_rung: bool = False, t0: int = 0,
+                   n: Optional[int] = None, per_series: bool = False):
+        """Pooled autocovariance sums of the window's series (fw_chains_series_acf): float64
+        [n_groups, max_lag + 3] = {sum over series of c[0..max_lag], of the means, of their
+        squares}; one group, or with ``by_rung`` one per rung.  ``per_series`` also returns
+        the exact int64 sums [n_series, 3, max_lag + 1] = {P, A, B}.  ``diagnostics`` turns
+        the pooled rows into autocorrelations, tau_int, ESS and R-hat."""
+        kind = SERIES_KINDS[what] if isinstance(what, str) else int(what)
+        t0, n = self._series_window(t0, n)
+        groups = self.n_rungs if by_rung and self.n_rungs else 1
+        pooled = np.empty((groups, int(max_lag) + 3), np.float64)
+        ps = np.empty((self.n_chains, 3, int(max_lag) + 1), np.int64) if per_series else None
+        check(_lib.load().fw_chains_series_acf(
+            self._h, kind | (_lib.SERIES_BY_RUNG if by_rung else 0), t0, n, int(max_lag),
+            ptr(ps), ptr(pooled)))
+        return (pooled, ps) if per_series else pooled
+
+    def run_sampled(self, steps_per_sample: int, n_samples: int,
+                    max_retries: int = DEFAULT_MAX_RETRIES) -> None:
+        """``n_samples`` x (``steps_per_sample`` steps, one recorded sample), enqueued back to
+        back and waited for once."""
+        L = _lib.load()
+        for _ in range(int(n_samples)):
+            check(L.fw_chains_run_async(self._h, int(steps_per_sample), int(max_retries)))
+            self.record()
+        self.sync()
 
     # ------------------------------------------------------------- sampled waits
     def enable_sampled_waits(self) -> None:
@@ -449,6 +547,14 @@ class Chains:
             ck["ladder_bases"], ck["set_of_chain"] = self.ladder_bases, self.set_of_chain
             ck["rung"], ck["rung_stats"] = self.rungs(), self.rung_stats()
             ck["ladder_round"] = np.int64(self.ladder_round)
+        if self.series_capacity:
+            info = self.series_info()
+            ck["series_capacity"] = np.int64(info["capacity"])
+            for kind in ("cut", "bnodes", "rung"):
+                ck["series_" + kind] = self.series(kind)
+            # which samples' rung rows belong to the current ladder (the by-rung view)
+            ck["series_valid"] = ((self._series_epoch[:info["n_samples"]] == info["epoch"]) &
+                                  (info["epoch"] > 0))
         return ck
 
     def restore(self, ck: dict) -> None:
@@ -509,6 +615,23 @@ class Chains:
                 raise ValueError("checkpoint of another ladder shape")
             check(L.fw_chains_write(self._h, _lib.READ_RUNG_STATS, ptr(a), a.nbytes))
             self.ladder_round = int(ck["ladder_round"])
+        # the series after the ladder: rung rows are checked against, and stamped with, it.
+        # Rung rows recorded under an earlier ladder are not carried (they read as -1).
+        if "series_capacity" in ck:
+            cut = np.ascontiguousarray(ck["series_cut"], np.int32)
+            if not self.series_capacity:
+                self.enable_series(int(ck["series_capacity"]))
+            elif self.series_capacity < cut.shape[0]:
+                raise ValueError(f"checkpoint of {cut.shape[0]} samples, handle holds "
+                                 f"{self.series_capacity}")
+            self.series_reset()
+            if cut.shape[0]:
+                self.write_series("cut", cut)
+                self.write_series("bnodes", ck["series_bnodes"])
+                valid = np.asarray(ck["series_valid"], bool)
+                edges = np.flatnonzero(np.diff(np.r_[False, valid, False].astype(np.int8)))
+                for lo, hi in zip(edges[::2], edges[1::2]):
+                    self.write_series("rung", ck["series_rung"][lo:hi], t0=int(lo))
 
     def save_checkpoint(self, path: str) -> None:
         ck = self.checkpoint()

@@ -187,6 +187,14 @@ struct fw_chains {
   int64_t* d_gmin = nullptr;
   FwRungSnap* d_snap = nullptr;
   fw_rung_stats* d_rstats = nullptr;
+  std::vector<int32_t> lad_set;  // set_of_chain of the current ladder
+  int64_t lad_epoch = 0;         // 0: no ladder; bumped by every fw_chains_set_ladder
+  // fw_chains_enable_series (ser_cap == 0: off): sample-major int32 [ser_cap][n_chains]
+  int64_t ser_cap = 0, ser_n = 0;
+  int32_t* d_ser_cut = nullptr;
+  int32_t* d_ser_bn = nullptr;
+  int32_t* d_ser_rung = nullptr;       // allocated on the first rung row (all -1 before it)
+  std::vector<int64_t> ser_epoch;      // [ser_cap] ladder epoch each sample's rung row belongs to
 };
 
 namespace {
@@ -491,7 +499,8 @@ void fw_chains_destroy(fw_chains* c) {
                   c->d_pend,   c->d_labval, c->d_flags, c->d_bcnt, c->d_sched, c->d_sched53,
                   c->d_ring,   c->d_ring_node, c->d_hist_ring, c->d_gscr, c->d_segdone,
                   c->d_wsamp,  c->d_wlp,   c->d_lad_thr, c->d_lad_thr53, c->d_logb, c->d_rung,
-                  c->d_chain_of, c->d_gmin, c->d_snap, c->d_rstats};
+                  c->d_chain_of, c->d_gmin, c->d_snap, c->d_rstats,
+                  c->d_ser_cut, c->d_ser_bn, c->d_ser_rung};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -1311,6 +1320,8 @@ int fw_chains_set_ladder(fw_chains* c, const double* thr_rows, const double* log
   c->p.thr53 = c->d_thr53;
   c->p.thr_stride = (int32_t)L;
   c->n_rungs = n_rungs;
+  c->lad_set.assign(set_of_chain, set_of_chain + C);
+  c->lad_epoch += 1;  // series samples recorded so far belong to the previous ladder
   return ladder_snapshot(c, st.data());
 }
 
@@ -1343,6 +1354,315 @@ int fw_chains_exchange_async(fw_chains* c, int64_t round) {
   if (le != 0)
     return fail(FW_EHIP, "exchange launch failed: %s", hipGetErrorString((hipError_t)le));
   return FW_OK;
+}
+
+// ---------------------------------------------------------------- observable series
+namespace {
+
+struct SeriesWhat {
+  int kind;
+  bool by_rung;
+};
+
+int series_what(int32_t what, SeriesWhat* w) {
+  if (what < 0 || (what & ~7) || (what & 3) == 3)
+    return fail(FW_EINVAL, "unknown series kind %d", what);
+  w->kind = what & 3;
+  w->by_rung = (what & FW_SERIES_BY_RUNG) != 0;
+  if (w->by_rung && w->kind == FW_SERIES_RUNG)
+    return fail(FW_EINVAL, "FW_SERIES_BY_RUNG applies to FW_SERIES_CUT and FW_SERIES_BNODES only");
+  return FW_OK;
+}
+
+int32_t* series_buf(fw_chains* c, int kind) {
+  return kind == FW_SERIES_CUT      ? c->d_ser_cut
+         : kind == FW_SERIES_BNODES ? c->d_ser_bn
+                                    : c->d_ser_rung;
+}
+
+// the rung rows, all -1 until something writes them (ordered on the handle's stream)
+int series_rung_alloc(fw_chains* c) {
+  if (c->d_ser_rung) return FW_OK;
+  const size_t bytes = sizeof(int32_t) * (size_t)c->ser_cap * (size_t)c->n_chains;
+  if (hipMalloc(&c->d_ser_rung, bytes) != hipSuccess) {
+    c->d_ser_rung = nullptr;
+    (void)hipGetLastError();
+    return fail(FW_ENOMEM, "rung series of %lld samples x %d chains", (long long)c->ser_cap,
+                c->n_chains);
+  }
+  HIPCHK(hipMemsetAsync(c->d_ser_rung, 0xFF, bytes, c->stream));
+  return FW_OK;
+}
+
+int series_window_ok(const fw_chains* c, int64_t t0, int64_t n, int64_t limit, const char* who) {
+  if (!c->ser_cap) return fail(FW_ESTATE, "%s: the series are not enabled", who);
+  if (t0 < 0 || n < 1 || t0 > limit || n > limit - t0)
+    return fail(FW_EINVAL, "%s: window [%lld, %lld + %lld) outside the %lld samples", who,
+                (long long)t0, (long long)t0, (long long)n, (long long)limit);
+  return FW_OK;
+}
+
+// Device pointer to the window [n][n_chains] of a view.  The plain view is the buffer itself;
+// the by-rung view is a regrouped copy (*tmp, to be freed by the caller).
+int series_view(fw_chains* c, SeriesWhat w, int64_t t0, int64_t n, const int32_t** x,
+                int32_t** tmp) {
+  const size_t C = (size_t)c->n_chains;
+  *tmp = nullptr;
+  if (!w.by_rung) {
+    *x = series_buf(c, w.kind) + (size_t)t0 * C;
+    return FW_OK;
+  }
+  if (!c->n_rungs) return fail(FW_ESTATE, "the by-rung view needs a ladder");
+  for (int64_t t = t0; t < t0 + n; ++t)
+    if (c->ser_epoch[(size_t)t] != c->lad_epoch)
+      return fail(FW_ESTATE, "sample %lld was not recorded under the current ladder",
+                  (long long)t);
+  int32_t* d_set = nullptr;
+  if (hipMalloc(tmp, sizeof(int32_t) * (size_t)n * C) != hipSuccess ||
+      hipMalloc(&d_set, sizeof(int32_t) * C) != hipSuccess) {
+    if (*tmp) (void)hipFree(*tmp);
+    *tmp = nullptr;
+    (void)hipGetLastError();
+    return fail(FW_ENOMEM, "by-rung view of %lld samples x %zu chains", (long long)n, C);
+  }
+  FwRegroupParams r{};
+  r.x = series_buf(c, w.kind) + (size_t)t0 * C;
+  r.rung = c->d_ser_rung + (size_t)t0 * C;
+  r.set_of = d_set;
+  r.out = *tmp;
+  r.n_chains = c->n_chains;
+  r.n_rungs = c->n_rungs;
+  r.n = n;
+  hipError_t e = hipMemcpyAsync(d_set, c->lad_set.data(), sizeof(int32_t) * C,
+                                hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = (hipError_t)fw_launch_regroup(r, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  (void)hipFree(d_set);
+  if (e != hipSuccess) {
+    (void)hipFree(*tmp);
+    *tmp = nullptr;
+    return fail(FW_EHIP, "by-rung regroup failed: %s", hipGetErrorString(e));
+  }
+  *x = *tmp;
+  return FW_OK;
+}
+
+}  // namespace
+
+int fw_chains_enable_series(fw_chains* c, int64_t capacity) {
+  if (!c) return fail(FW_EINVAL, "null handle");
+  if (capacity < 1) return fail(FW_EINVAL, "series capacity %lld < 1", (long long)capacity);
+  if (c->ser_cap) return fail(FW_ESTATE, "the series are already enabled");
+  HIPCHK(hipSetDevice(c->g->device));
+  const size_t C = (size_t)c->n_chains;
+  if ((size_t)capacity > SIZE_MAX / sizeof(int32_t) / C)
+    return fail(FW_ENOMEM, "series of %lld samples x %zu chains", (long long)capacity, C);
+  const size_t bytes = sizeof(int32_t) * (size_t)capacity * C;
+  int32_t *a = nullptr, *b = nullptr;
+  if (hipMalloc(&a, bytes) != hipSuccess || hipMalloc(&b, bytes) != hipSuccess) {
+    if (a) (void)hipFree(a);
+    (void)hipGetLastError();
+    return fail(FW_ENOMEM, "series of %lld samples x %zu chains", (long long)capacity, C);
+  }
+  if (hipMemset(a, 0, bytes) != hipSuccess || hipMemset(b, 0, bytes) != hipSuccess) {
+    (void)hipFree(a);
+    (void)hipFree(b);
+    return fail(FW_EHIP, "series clear failed");
+  }
+  c->d_ser_cut = a;
+  c->d_ser_bn = b;
+  c->ser_epoch.assign((size_t)capacity, 0);
+  c->ser_cap = capacity;
+  c->ser_n = 0;
+  return FW_OK;
+}
+
+int fw_chains_record_async(fw_chains* c) {
+  if (!c) return fail(FW_EINVAL, "null handle");
+  if (!c->ser_cap) return fail(FW_ESTATE, "fw_chains_record_async: the series are not enabled");
+  if (c->ser_n >= c->ser_cap)
+    return fail(FW_ESTATE, "fw_chains_record_async: all %lld samples are taken",
+                (long long)c->ser_cap);
+  HIPCHK(hipSetDevice(c->g->device));
+  if (c->n_rungs)
+    if (const int rc = series_rung_alloc(c)) return rc;
+  FwRecordParams r{};
+  r.stats = c->d_stats;
+  r.rung = c->n_rungs ? c->d_rung : nullptr;
+  r.cut = c->d_ser_cut;
+  r.bnodes = c->d_ser_bn;
+  r.rung_out = c->d_ser_rung;
+  r.n_chains = c->n_chains;
+  r.sample = c->ser_n;
+  // like the exchange step: the run timing events are left alone
+  const int le = fw_launch_record(r, c->stream);
+  if (le != 0) return fail(FW_EHIP, "record launch failed: %s", hipGetErrorString((hipError_t)le));
+  c->ser_epoch[(size_t)c->ser_n] = c->lad_epoch;
+  c->ser_n += 1;
+  return FW_OK;
+}
+
+int fw_chains_series_info(const fw_chains* c, int64_t info[4]) {
+  if (!c || !info) return fail(FW_EINVAL, "fw_chains_series_info: null");
+  info[0] = c->ser_cap;
+  info[1] = c->ser_n;
+  info[2] = c->lad_epoch;
+  info[3] = c->n_rungs;
+  return FW_OK;
+}
+
+int fw_chains_series_reset(fw_chains* c) {
+  if (!c) return fail(FW_EINVAL, "null handle");
+  if (!c->ser_cap) return fail(FW_ESTATE, "fw_chains_series_reset: the series are not enabled");
+  c->ser_n = 0;
+  return FW_OK;
+}
+
+int fw_chains_read_series(fw_chains* c, int32_t what, int64_t t0, int64_t n, int32_t* dst,
+                          size_t bytes) {
+  if (!c || !dst) return fail(FW_EINVAL, "fw_chains_read_series: null");
+  SeriesWhat w;
+  if (const int rc = series_what(what, &w)) return rc;
+  if (const int rc = series_window_ok(c, t0, n, c->ser_n, "fw_chains_read_series")) return rc;
+  const size_t C = (size_t)c->n_chains, need = sizeof(int32_t) * (size_t)n * C;
+  if (bytes < need) return fail(FW_EINVAL, "the window needs %zu bytes", need);
+  HIPCHK(hipSetDevice(c->g->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (w.kind == FW_SERIES_RUNG && !c->d_ser_rung) {  // no rung row was ever kept
+    std::fill(dst, dst + (size_t)n * C, -1);
+    return FW_OK;
+  }
+  const int32_t* x = nullptr;
+  int32_t* tmp = nullptr;
+  if (const int rc = series_view(c, w, t0, n, &x, &tmp)) return rc;
+  const hipError_t e = hipMemcpy(dst, x, need, hipMemcpyDeviceToHost);
+  if (tmp) (void)hipFree(tmp);
+  if (e != hipSuccess) return fail(FW_EHIP, "series download failed: %s", hipGetErrorString(e));
+  return FW_OK;
+}
+
+int fw_chains_write_series(fw_chains* c, int32_t what, int64_t t0, int64_t n, const int32_t* src,
+                           size_t bytes) {
+  if (!c || !src) return fail(FW_EINVAL, "fw_chains_write_series: null");
+  SeriesWhat w;
+  if (const int rc = series_what(what, &w)) return rc;
+  if (w.by_rung) return fail(FW_EINVAL, "series are written by chain, not by rung");
+  if (const int rc = series_window_ok(c, t0, n, c->ser_cap, "fw_chains_write_series")) return rc;
+  if (t0 > c->ser_n)
+    return fail(FW_EINVAL, "a write at sample %lld would leave a gap after the %lld recorded",
+                (long long)t0, (long long)c->ser_n);
+  const size_t C = (size_t)c->n_chains, need = sizeof(int32_t) * (size_t)n * C;
+  if (bytes < need) return fail(FW_EINVAL, "the window needs %zu bytes", need);
+  if (w.kind != FW_SERIES_RUNG) {  // what the exact sums' overflow bound rests on
+    const int64_t xmax = std::max<int64_t>(c->g->nnz / 2, c->g->n);
+    for (size_t i = 0; i < (size_t)n * C; ++i)
+      if (src[i] < 0 || src[i] > xmax)
+        return fail(FW_EINVAL, "sample %lld, chain %zu: value %d outside [0, %lld]",
+                    (long long)(t0 + (int64_t)(i / C)), i % C, src[i], (long long)xmax);
+  } else if (c->n_rungs) {  // every (set, rung) exactly once per sample
+    const int R = c->n_rungs;
+    std::vector<int64_t> seen(C, -1);
+    for (int64_t t = 0; t < n; ++t)
+      for (size_t i = 0; i < C; ++i) {
+        const int r = src[(size_t)t * C + i];
+        if (r < 0 || r >= R)
+          return fail(FW_EINVAL, "sample %lld, chain %zu: rung %d outside [0, %d)",
+                      (long long)(t0 + t), i, r, R);
+        int64_t& s = seen[(size_t)c->lad_set[i] * R + r];
+        if (s == t)
+          return fail(FW_EINVAL, "sample %lld: rung %d of set %d is held twice",
+                      (long long)(t0 + t), r, c->lad_set[i]);
+        s = t;
+      }
+  }
+  HIPCHK(hipSetDevice(c->g->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (w.kind == FW_SERIES_RUNG)
+    if (const int rc = series_rung_alloc(c)) return rc;
+  const int64_t end = t0 + n;
+  if (w.kind != FW_SERIES_RUNG && c->d_ser_rung && end > c->ser_n)
+    // samples a value write creates carry no rung row
+    HIPCHK(hipMemsetAsync(c->d_ser_rung + (size_t)c->ser_n * C, 0xFF,
+                          sizeof(int32_t) * (size_t)(end - c->ser_n) * C, c->stream));
+  HIPCHK(hipMemcpyAsync(series_buf(c, w.kind) + (size_t)t0 * C, src, need, hipMemcpyHostToDevice,
+                        c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int64_t t = t0; t < end; ++t)
+    if (w.kind == FW_SERIES_RUNG)
+      c->ser_epoch[(size_t)t] = c->lad_epoch;
+    else if (t >= c->ser_n)
+      c->ser_epoch[(size_t)t] = 0;
+  c->ser_n = std::max(c->ser_n, end);
+  return FW_OK;
+}
+
+int fw_chains_series_acf(fw_chains* c, int32_t what, int64_t t0, int64_t n, int32_t max_lag,
+                         int64_t* per_series, double* pooled) {
+  if (!c) return fail(FW_EINVAL, "null handle");
+  SeriesWhat w;
+  if (const int rc = series_what(what, &w)) return rc;
+  if (w.kind == FW_SERIES_RUNG)
+    return fail(FW_EINVAL, "autocovariances are taken of FW_SERIES_CUT or FW_SERIES_BNODES");
+  if (const int rc = series_window_ok(c, t0, n, c->ser_n, "fw_chains_series_acf")) return rc;
+  if (max_lag < 0 || max_lag >= n)
+    return fail(FW_EINVAL, "max_lag %d outside [0, n = %lld)", max_lag, (long long)n);
+  if (max_lag > FW_SERIES_MAX_LAG)
+    return fail(FW_EINVAL, "max_lag %d above %d", max_lag, FW_SERIES_MAX_LAG);
+  const int64_t xmax = std::max<int64_t>(c->g->nnz / 2, c->g->n);
+  if ((unsigned __int128)n * (unsigned __int128)xmax * (unsigned __int128)xmax >=
+      ((unsigned __int128)1 << 63))
+    return fail(FW_EINVAL, "n * xmax^2 = %lld * %lld^2 does not fit 63 bits", (long long)n,
+                (long long)xmax);
+  HIPCHK(hipSetDevice(c->g->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const int32_t* x = nullptr;
+  int32_t* tmp = nullptr;
+  if (const int rc = series_view(c, w, t0, n, &x, &tmp)) return rc;
+  const size_t C = (size_t)c->n_chains, L1 = (size_t)max_lag + 1;
+  const int n_groups = w.by_rung ? c->n_rungs : 1;
+  int64_t* d_sums = nullptr;
+  double* d_pool = nullptr;
+  int rc = FW_OK;
+  if (hipMalloc(&d_sums, sizeof(int64_t) * 3 * L1 * C) != hipSuccess ||
+      hipMalloc(&d_pool, sizeof(double) * (size_t)n_groups * (L1 + 2)) != hipSuccess) {
+    (void)hipGetLastError();
+    rc = fail(FW_ENOMEM, "lagged sums of %zu series x %zu lags", C, L1);
+  }
+  if (rc == FW_OK) {
+    FwAcfParams a{};
+    a.x = x;
+    a.sums = d_sums;
+    a.n_series = c->n_chains;
+    a.max_lag = max_lag;
+    a.n = n;
+    FwPoolParams p{};
+    p.sums = d_sums;
+    p.out = d_pool;
+    p.n_series = c->n_chains;
+    p.max_lag = max_lag;
+    p.members = w.by_rung ? c->n_chains / c->n_rungs : c->n_chains;
+    p.stride = w.by_rung ? c->n_rungs : 1;
+    p.n = n;
+    hipError_t e = (hipError_t)fw_launch_acf(a, c->stream);
+    if (e == hipSuccess && pooled) e = (hipError_t)fw_launch_pool(p, n_groups, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess && pooled)
+      e = hipMemcpy(pooled, d_pool, sizeof(double) * (size_t)n_groups * (L1 + 2),
+                    hipMemcpyDeviceToHost);
+    if (e == hipSuccess && per_series) {
+      // device layout [3][L1][series] (coalesced along the series) -> [series][3][L1]
+      std::vector<int64_t> h(3 * L1 * C);
+      e = hipMemcpy(h.data(), d_sums, sizeof(int64_t) * h.size(), hipMemcpyDeviceToHost);
+      if (e == hipSuccess)
+        for (size_t kl = 0; kl < 3 * L1; ++kl)
+          for (size_t j = 0; j < C; ++j) per_series[j * 3 * L1 + kl] = h[kl * C + j];
+    }
+    if (e != hipSuccess) rc = fail(FW_EHIP, "series_acf failed: %s", hipGetErrorString(e));
+  }
+  if (d_sums) (void)hipFree(d_sums);
+  if (d_pool) (void)hipFree(d_pool);
+  if (tmp) (void)hipFree(tmp);
+  return rc;
 }
 
 int fw_chains_enable_ring(fw_chains* c, const int32_t* ring_u, const int32_t* ring_w,

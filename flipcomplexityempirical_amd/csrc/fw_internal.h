@@ -189,6 +189,61 @@ struct FwExchangeParams {
   uint64_t seed;
 };
 
+// ---- thinned observable series (fw_chains_enable_series, fw_series.hip) ----------------
+// Series buffers are sample-major int32 [capacity][n_chains]: a wave's 64 lanes touch 64
+// adjacent chains of one sample (256 B).
+#define FW_SERIES_MAX_LAG 1023
+#define FW_ACF_CHUNK 32   // lags per wave of the autocovariance kernel
+#define FW_ACF_WAVES 4    // waves (lag chunks) per workgroup, all on the same 64 series
+#define FW_POOL_WIDTH 256 // sequential partials of the pooled sums
+
+// fw_chains_record_async: sample `sample` of every chain
+struct FwRecordParams {
+  const fw_chain_stats* stats;  // [n_chains]
+  const int32_t* rung;          // [n_chains] or null (no ladder: -1 is recorded)
+  int32_t* cut;                 // [capacity][n_chains]
+  int32_t* bnodes;
+  int32_t* rung_out;            // null when no rung row is kept
+  int32_t n_chains;
+  int64_t sample;
+};
+
+// by-rung view of a window: out[t][set_of[c] * n_rungs + rung[t][c]] = x[t][c]
+struct FwRegroupParams {
+  const int32_t* x;       // window start, [n][n_chains]
+  const int32_t* rung;    // window start, [n][n_chains]
+  const int32_t* set_of;  // [n_chains]
+  int32_t* out;           // [n][n_chains]
+  int32_t n_chains, n_rungs;
+  int64_t n;
+};
+
+// exact lagged sums of a window: sums[(k * (max_lag + 1) + l) * n_series + j], k = 0 (P),
+// 1 (A), 2 (B) of include/flipwalk.h; lag-major on the device so that stores and the pooling
+// loads are coalesced along the series index (the host transposes for per_series)
+struct FwAcfParams {
+  const int32_t* x;  // window start, [n][n_series]
+  int64_t* sums;
+  int32_t n_series, max_lag;
+  int64_t n;
+};
+
+// pooled autocovariances: out[g][0..max_lag] = sum of c_j[l], out[g][max_lag+1] = sum of m_j,
+// out[g][max_lag+2] = sum of m_j^2 over the members j = first + pos * stride, pos < members,
+// of group g (first = g), in the order include/flipwalk.h states
+struct FwPoolParams {
+  const int64_t* sums;
+  double* out;  // [n_groups][max_lag + 3]
+  int32_t n_series, max_lag, members, stride;
+  int64_t n;
+};
+
+// Host-side launchers implemented in fw_series.hip.
+int fw_launch_record(const FwRecordParams& r, void* stream);
+int fw_launch_regroup(const FwRegroupParams& r, void* stream);
+int fw_launch_acf(const FwAcfParams& a, void* stream);
+int fw_launch_pool(const FwPoolParams& p, int n_groups, void* stream);
+
 // Host-side launchers implemented in fw_kernels.hip.
 int fw_launch_exchange(const FwExchangeParams& e, void* stream);
 int fw_launch_map_init(const FwRunParams& p, void* stream);

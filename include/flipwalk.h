@@ -164,11 +164,13 @@ const char* fw_last_error(void);
 /* Library/ABI version, e.g. 0x000600 for 0.6.0 (0.2: spatial maps; 0.3: bound
  * schedules; 0.4: ring observable, checkpoint/resume; 0.5: sampled geometric waits;
  * 0.6: fw_chains_launch_info; 0.7: fw_build_info; the ladder entry points
- * fw_chains_set_ladder / fw_chains_exchange_async arrived in 0.7 without a bump). */
+ * fw_chains_set_ladder / fw_chains_exchange_async and the observable-series entry points
+ * arrived in 0.7 without a bump). */
 int32_t fw_version(void);
 
-/* Provenance of this build (static string, never NULL): "src=<sha256 of every kernel,
- * header and ABI source> flags=<compiler flags, including any -D>".  Bench lines and PMC
+/* Provenance of this build (static string, never NULL): "src=<sha256 of the flip
+ * kernels, headers and ABI source> flags=<compiler flags, including any -D>
+ * series=<sha256 of fw_series.hip>".  Bench lines and PMC
  * profiles carry it, so a measurement names the code it measured. */
 const char* fw_build_info(void);
 
@@ -248,7 +250,8 @@ int fw_chains_read(fw_chains* c, int32_t what, void* host_dst, size_t bytes);
  * write also restores the yield count the maps' 2^32 index guard starts from. */
 int fw_chains_write(fw_chains* c, int32_t what, const void* host_src, size_t bytes);
 
-/* Zero the per-chain sums and the yield histograms (not the chain states). */
+/* Zero the per-chain sums and the yield histograms (not the chain states, and not the
+ * observable series: fw_chains_series_reset). */
 int fw_chains_reset_observables(fw_chains* c);
 
 /* Select the accept rule (FW_ACCEPT_*) for every chain; node_flags [n] (1 =
@@ -335,6 +338,78 @@ int fw_chains_set_ladder(fw_chains* c, const double* thr_rows /*[n_rungs][2*maxd
                          const double* log_base /*[n_rungs]*/, int32_t n_rungs,
                          const int32_t* set_of_chain, const int32_t* rung_of_chain);
 int fw_chains_exchange_async(fw_chains* c, int64_t round);
+
+/* ---- thinned observable series ------------------------------------------------------
+ * The reference keeps rce, rbn and waits as per-yield lists (grid_chain_sec11.py:350-369) and
+ * plots them as traces; the sums and histograms above drop the order in time.  A series keeps
+ * it, thinned: one sample of every chain's current len(cut_edges) and len(b_nodes) wherever
+ * the caller asks for one between launches, as the exchange step is placed.
+ *
+ * fw_chains_enable_series (once per handle: FW_ESTATE the second time; capacity >= 1;
+ * FW_ENOMEM) allocates sample-major device buffers int32 [capacity][n_chains] for cut and
+ * bnodes; the rung buffer of the same shape is allocated on the first rung row (a recorded
+ * sample of a laddered handle, or a FW_SERIES_RUNG write) and reads as -1 before it.
+ *
+ * fw_chains_record_async enqueues one small kernel on the handle's stream (no host
+ * synchronisation; fw_chains_last_kernel_ms is not touched) that writes sample n_samples of
+ * every chain: cut and bnodes from the stats records, rung from the ladder (-1 without one);
+ * n_samples is incremented at enqueue.  FW_ESTATE when the series are not enabled or full.
+ * The host stamps each sample with the ladder epoch it was recorded under: 0 without a ladder,
+ * and every fw_chains_set_ladder starts the next epoch.
+ *
+ * fw_chains_series_info: info[0] = capacity (0: not enabled), info[1] = n_samples,
+ * info[2] = the current ladder epoch, info[3] = n_rungs.
+ *
+ * fw_chains_read_series / fw_chains_write_series move the window [t0, t0 + n), n >= 1, of
+ * `what` = FW_SERIES_CUT, FW_SERIES_BNODES or FW_SERIES_RUNG.  The plain view is int32
+ * [n][n_chains], by chain.  A read of CUT or BNODES or'ed with FW_SERIES_BY_RUNG is
+ * [n][n_sets * n_rungs]: slot set * n_rungs + r of sample t holds the value of the chain that
+ * sat on rung r of that set when sample t was taken; it needs a ladder and every sample of the
+ * window stamped with the current epoch (FW_ESTATE otherwise).  A read window must lie inside
+ * [0, n_samples), a write window inside [0, capacity) with t0 <= n_samples (no gaps), else
+ * FW_EINVAL; a write sets n_samples = max(n_samples, t0 + n).  Writes exist for checkpoints
+ * and tests: CUT / BNODES values must lie in [0, xmax], xmax = max(n_edges, n nodes) (what
+ * any recorded value satisfies), else FW_EINVAL; a sample such a write creates has no rung row
+ * (-1, epoch 0).  A RUNG write on a laddered handle must hold every (set, rung) exactly once
+ * per sample (FW_EINVAL) and stamps its samples with the current epoch; without a ladder the
+ * values are taken as they are, under epoch 0.
+ *
+ * fw_chains_series_reset sets n_samples = 0.  fw_chains_reset_observables does NOT touch the
+ * series.
+ *
+ * fw_chains_series_acf (`what` = CUT or BNODES, optionally | FW_SERIES_BY_RUNG) synchronises
+ * the stream and reduces the window's n_series = n_chains series x_j[0..n):
+ *  1. per_series, int64 [n_series][3][max_lag + 1] = {P, A, B}, exact:
+ *       P[j][l] = sum_{t=0}^{n-1-l} x_t * x_{t+l}
+ *       A[j][l] = sum_{t=0}^{n-1-l} x_t          B[j][l] = sum_{t=l}^{n-1} x_t
+ *     FW_EINVAL unless 0 <= max_lag < n, max_lag <= 1023 and n * xmax^2 < 2^63.
+ *  2. pooled, double [n_groups][max_lag + 3] = {sum_j c_j[0..max_lag], sum_j m_j, sum_j m_j^2}
+ *     in plain IEEE double operations (no contraction), evaluated exactly in this order:
+ *       m_j    = (double)A[j][0] / (double)n
+ *       c_j[l] = (((double)P - m_j * (double)(A + B)) + (double)(n - l) * m_j * m_j) / (double)n
+ *     ((double)(n - l) * m_j first, then * m_j; A + B added as integers), summed over the
+ *     members of a group in a fixed order: partial p, p = 0..255, is the sequential sum,
+ *     from +0.0 and in ascending position, of the members whose position = p (mod 256); then
+ *     the halving tree a[i] += a[i + 128], then 64, .., 1, and a[0] is the sum.
+ *     Plain view: one group, every chain in ascending index.  By-rung view: n_rungs groups,
+ *     group r = slots set * n_rungs + r in ascending set.
+ * Either output may be NULL.  The kernels use no atomics and do not depend on thread order:
+ * a host restatement of the above agrees bit for bit.
+ * (These entry points arrived in 0.7 without a version bump.) */
+#define FW_SERIES_CUT 0
+#define FW_SERIES_BNODES 1
+#define FW_SERIES_RUNG 2
+#define FW_SERIES_BY_RUNG 4
+int fw_chains_enable_series(fw_chains* c, int64_t capacity);
+int fw_chains_record_async(fw_chains* c);
+int fw_chains_series_info(const fw_chains* c, int64_t info[4]);
+int fw_chains_series_reset(fw_chains* c);
+int fw_chains_read_series(fw_chains* c, int32_t what, int64_t t0, int64_t n, int32_t* dst,
+                          size_t bytes);
+int fw_chains_write_series(fw_chains* c, int32_t what, int64_t t0, int64_t n, const int32_t* src,
+                           size_t bytes);
+int fw_chains_series_acf(fw_chains* c, int32_t what, int64_t t0, int64_t n, int32_t max_lag,
+                         int64_t* per_series, double* pooled);
 
 /* Read a map (FW_MAP_*) of chains [chain0, chain0 + n_chains) as int64
  * [n_chains][len], or with FW_MAP_SUM its sum over those chains [len]; len is
