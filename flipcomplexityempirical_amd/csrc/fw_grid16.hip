@@ -81,8 +81,9 @@ static_assert(offsetof(fw_chain_stats, yields) == 88 && offsetof(fw_chain_stats,
 // Pickers of the instantiations compiled in their own translation units (the Makefile
 // schedules each differently): fw_grid16_lean.hip the small-grid lean kernels,
 // fw_grid16_w2.hip the W2 ones.  The stamps build compiles everything here.
-void* fw_grid16_pick_lean(int lb, int mode, int G);
-void* fw_grid16_pick_w2(int mode, int G);
+// (w4: the grid width is a multiple of 4)
+void* fw_grid16_pick_lean(int lb, int mode, int G, bool w4);
+void* fw_grid16_pick_w2(int mode, int G, bool w4);
 
 namespace {
 
@@ -227,7 +228,10 @@ __device__ __forceinline__ uint32_t byte_popc(uint32_t f) {  // per-byte popcoun
   return (t & 0x33333333u) + ((t >> 2) & 0x33333333u);
 }
 
-template <int MODE, bool NEED_CD, bool BATCH = true>
+// W4: the grid width is a multiple of 4 (the plan's pick: C3's 100, C2's 40), so the four
+// nodes of a lane never straddle a grid row and every mask is all-or-nothing per neighbour
+// (left / right: one fixed byte).
+template <int MODE, bool NEED_CD, bool BATCH = true, bool W4 = false>
 __device__ __forceinline__ void weights4_swar(const LDS uint8_t* lab, int x0, int W, int H, int n,
                                               GDiv gd, uint32_t& w4, uint32_t& cd4) {
   w4 = 0;
@@ -259,13 +263,23 @@ __device__ __forceinline__ void weights4_swar(const LDS uint8_t* lab, int x0, in
   // column-(W-1) byte (byte tw - 1 when tw <= 4).  Bytes past n (row H and beyond) are
   // cleared by mN, so row H - 1 may clear its next-row bytes too.  Equal to the per-byte
   // clamp/select form after the & mN on every grid W >= 4, H <= 40, all groups (host check).
-  const uint32_t t8 = (uint32_t)min(tw, 4) << 3;
-  const uint32_t nxt = (uint32_t)(~0ull << t8);
-  const uint32_t mN = low_bytes(n - x0);
-  const uint32_t mU = r0 > 0 ? 0xFFFFFFFFu : nxt;
-  const uint32_t mD = r0 < H - 2 ? 0xFFFFFFFFu : (r0 == H - 2 ? ~nxt : 0u);
-  const uint32_t mL = ~((uint32_t)(0xFFull << t8) | (c0 == 0 ? 0xFFu : 0u));
-  const uint32_t mR = ~(uint32_t)(0xFFull << (((uint32_t)min(tw, 5) << 3) - 8u));
+  uint32_t mN, mU, mD, mL, mR;
+  if constexpr (W4) {
+    // x0, W and n are multiples of 4: c0 + 3 < W, and the group tail past n is whole lanes
+    mN = x0 < n ? 0xFFFFFFFFu : 0u;
+    mU = r0 > 0 ? 0xFFFFFFFFu : 0u;
+    mD = r0 < H - 1 ? 0xFFFFFFFFu : 0u;
+    mL = c0 == 0 ? 0xFFFFFF00u : 0xFFFFFFFFu;
+    mR = tw == 4 ? 0x00FFFFFFu : 0xFFFFFFFFu;
+  } else {
+    const uint32_t t8 = (uint32_t)min(tw, 4) << 3;
+    const uint32_t nxt = (uint32_t)(~0ull << t8);
+    mN = low_bytes(n - x0);
+    mU = r0 > 0 ? 0xFFFFFFFFu : nxt;
+    mD = r0 < H - 2 ? 0xFFFFFFFFu : (r0 == H - 2 ? ~nxt : 0u);
+    mL = ~((uint32_t)(0xFFull << t8) | (c0 == 0 ? 0xFFu : 0u));
+    mR = ~(uint32_t)(0xFFull << (((uint32_t)min(tw, 5) << 3) - 8u));
+  }
   if constexpr (BATCH) __builtin_amdgcn_sched_barrier(0);  // not needed under the W2 budget
   uint32_t win[3];
 #pragma unroll
@@ -294,11 +308,11 @@ __device__ __forceinline__ void weights4_swar(const LDS uint8_t* lab, int x0, in
 }
 
 // weights (and, when NEED_CD, cut degrees) of nodes x0..x0+3, one per byte
-template <int LB, int MODE, bool NEED_CD, bool BATCH = true>
+template <int LB, int MODE, bool NEED_CD, bool BATCH = true, bool W4 = false>
 __device__ __forceinline__ void weights4x(const LDS uint8_t* lab, int x0, int W, int H, int n,
                                           GDiv gd, uint32_t& w4, uint32_t& cd4) {
   if constexpr (LB == 2)
-    weights4_swar<MODE, NEED_CD, BATCH>(lab, x0, W, H, n, gd, w4, cd4);
+    weights4_swar<MODE, NEED_CD, BATCH, W4>(lab, x0, W, H, n, gd, w4, cd4);
   else
     weights4<LB, MODE>(lab, x0, W, H, n, gd, w4, cd4);
 }
@@ -621,8 +635,12 @@ __device__ bool grid_race(const LDS uint8_t* lab, LDS uint8_t* scr, LDS uint32_t
 // trajectories, counters and sums stay bit-identical.  It raises the attempts per chain
 // per wave iteration (C3: 1.56 at R = 2, 2.05 at R = 4) where too few chains are left to
 // fill the GPU: an 8,192-chain shard leaves a third of the wave slots empty at R = 1.
-template <int LB, int MODE, int PER, bool FULL, bool BIG, int R, bool W2 = false>
+//
+// W4 (2-bit labels, lean R = 1 and W2 instantiations): the grid width is a multiple of 4
+// (weights4_swar's short masks).
+template <int LB, int MODE, int PER, bool FULL, bool BIG, int R, bool W2 = false, bool W4 = false>
 __device__ __forceinline__ void grid16_body(const FwRunParams& p) {
+  static_assert(!W4 || LB == 2, "the width flag belongs to the SWAR weights");
   static_assert(PER % 2 == 0, "group sums are read as u16 pairs");
   static_assert(R == 1 || R == 2 || R == 4, "rows per chain");
   static_assert(R == 1 || (!FULL && !BIG), "speculation: lean small-grid kernels only");
@@ -770,7 +788,11 @@ __device__ __forceinline__ void grid16_body(const FwRunParams& p) {
     uint32_t n_att = 0;
     const uint64_t yields0 = stp->yields;
     int32_t stuck = has ? stp->stuck : 1;
-    int64_t sum_cut = stp->sum_cut, sum_bnodes = stp->sum_bnodes;
+    // this unit's sums of cut and |B| over its yields, in 32 bits: folded into the record's
+    // 64-bit totals with the attempt counters (below) and at the write-back.  Between two
+    // Philox refills they grow by at most 64 yields x 2^17 (cut < 2 n <= 2^17), so a fold at
+    // the first refill past p.fold_at (2^31; tests lower it) keeps them from wrapping.
+    uint32_t s_cut = 0, s_bn = 0;
     double sum_invb = stp->sum_invb;
     // sampled geometric waits (FULL only): the running sum and the current state's draw
     const bool waits_on = FULL && p.wsamp != nullptr;
@@ -795,7 +817,7 @@ __device__ __forceinline__ void grid16_body(const FwRunParams& p) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           uint32_t w4, cd4;
-          weights4x<LB, MODE, true>(lab, (2 * t2 + h) * 64 + q * 4, W, H, n, gd, w4, cd4);
+          weights4x<LB, MODE, true, true, W4>(lab, (2 * t2 + h) * 64 + q * 4, W, H, n, gd, w4, cd4);
           const uint32_t ws = bsum4m(w4);
           cut2 += bsum4m(cd4);
           bn += ((cd4 & 0xFFu) != 0) + ((cd4 & 0xFF00u) != 0) + ((cd4 & 0xFF0000u) != 0) +
@@ -871,8 +893,8 @@ __device__ __forceinline__ void grid16_body(const FwRunParams& p) {
       if (!on) return;
       if (FULL) rrun += 1;
       if (waits_on) wsum += wcur;
-      sum_cut += cut;
-      sum_bnodes += bnodes;
+      s_cut += (uint32_t)cut;
+      s_bn += (uint32_t)bnodes;
       sum_invb += invb;
       int ic = cut - base_c;
       if (ic < 0 || ic >= 2 * ROW) {
@@ -904,6 +926,17 @@ __device__ __forceinline__ void grid16_body(const FwRunParams& p) {
     // (row_shl:1), all DPP; a row that stops stays stopped for this launch.
     U4 pb = {0u, 0u, 0u, 0u};
     int bpos = ROW;
+    // The lane's level-1 words (group sums, BIG: supergroup sums; words past GW (SG) are zero
+    // padding) are carried across the loop's back edge: they depend on no value of the draw,
+    // only on the previous commit's lds_add, and a wave's LDS operations complete in order,
+    // so a read issued right after the commit returns the committed sums while its latency
+    // hides behind the observation, the counters and the next draw.
+    uint32_t w2[PER / 2];
+    auto read_lvl1 = [&]() {
+#pragma unroll
+      for (int t = 0; t < PER / 2; ++t) w2[t] = lvl1[q * (PER / 2) + t];
+    };
+    read_lvl1();
 
     const bool unit_pop = !FULL || p.g.pop == nullptr;  // node populations: FULL only
     // Wave priority by progress.  A SIMD issues VALU to the higher-priority wave, then the
@@ -939,14 +972,17 @@ __device__ __forceinline__ void grid16_body(const FwRunParams& p) {
       U4 x;
       if constexpr (R == 1) {
         if (bpos == ROW) {
-          if (n_sdeg >= p.fold_at) {  // rare: fold (see att0); one row at a time
+          if (n_sdeg >= p.fold_at || (s_cut | s_bn) >= p.fold_at) {  // rare: fold (see att0); one row at a time
             if (q == 0 && has) {
               stp->pop_fail += n_popf;
               stp->contig_fail += n_conf;
               stp->sum_deg += n_sdeg;
+              stp->sum_cut += s_cut;
+              stp->sum_bnodes += s_bn;
             }
             att0 += n_att;
             n_att = n_popf = n_conf = n_sdeg = 0;
+            s_cut = s_bn = 0;
           }
           const uint64_t t = att0 + (uint64_t)(n_att + (uint32_t)q);
           pb = philox((uint32_t)t, (uint32_t)(t >> 32), (uint32_t)gid, (uint32_t)(gid >> 32),
@@ -963,16 +999,22 @@ __device__ __forceinline__ void grid16_body(const FwRunParams& p) {
         // takes attempt bpos_w + s; refilled from the next unconsumed attempt when fewer
         // than R are left
         if (bpos_w > (uint32_t)(ROW * R - R)) {
-          if (4u * n_att >= p.fold_at) {  // rare (grids: degree <= 4): fold, group-uniform
+          // rare (grids: degree <= 4): fold, group-uniform (the owner row keeps the sums; the
+          // group's rows test the owner's)
+          const uint32_t s_any = lane_read(s_cut | s_bn, gb + q);
+          if (4u * n_att >= p.fold_at || s_any >= p.fold_at) {
             const uint32_t f0 = grp_sum<R>(n_popf, gb, q), f1 = grp_sum<R>(n_conf, gb, q);
             const uint32_t f2 = grp_sum<R>(n_sdeg, gb, q);
             if (q == 0 && owner && has) {
               stp->pop_fail += f0;
               stp->contig_fail += f1;
               stp->sum_deg += f2;
+              stp->sum_cut += s_cut;
+              stp->sum_bnodes += s_bn;
             }
             att0 += n_att;
             n_att = n_popf = n_conf = n_sdeg = 0;
+            s_cut = s_bn = 0;
           }
           const uint64_t t = att0 + (uint64_t)(n_att + (uint32_t)(sx * ROW + q));
           pb = philox((uint32_t)t, (uint32_t)(t >> 32), (uint32_t)gid, (uint32_t)(gid >> 32),
@@ -986,14 +1028,11 @@ __device__ __forceinline__ void grid16_body(const FwRunParams& p) {
       const uint32_t r = scale64(x.x0, x.x1, (uint32_t)(npairs > 0 ? npairs : 1));
 
       STAMP(0);  // draw
-      // ---- select, level 1: group sums (PER per lane, read as PER/2 u16 pairs)
-      uint32_t w2[PER / 2];
+      // ---- select, level 1: group sums (PER per lane, PER/2 u16 pairs: w2, read after the
+      //      previous iteration's commit)
       uint32_t s = 0;
 #pragma unroll
-      for (int t = 0; t < PER / 2; ++t) {
-        w2[t] = lvl1[q * (PER / 2) + t];  // words past GW (SG) are zero padding
-        s += (w2[t] & 0xFFFFu) + (w2[t] >> 16);
-      }
+      for (int t = 0; t < PER / 2; ++t) s += (w2[t] & 0xFFFFu) + (w2[t] >> 16);
       // packed u16 prefixes of the lane's groups, pair t = (c_{2t+1}, c_{2t+2}) with c_j the
       // sum of its first j groups (< 2^15 on the chosen lane: <= 16 groups of <= 64 x 4, or
       // BIG's <= 4 supergroups of <= 16 x 192); independent of r, so they fill the scan's
@@ -1054,7 +1093,7 @@ __device__ __forceinline__ void grid16_body(const FwRunParams& p) {
       // ---- select, level 2: weights of the group's 64 nodes, 4 per lane
       const int x0 = gi * 64 + q * 4;
       uint32_t w4, cd4;  // four 8-bit weights
-      weights4x<LB, MODE, false, !W2>(lab, x0, W, H, n, gd, w4, cd4);
+      weights4x<LB, MODE, false, !W2, W4>(lab, x0, W, H, n, gd, w4, cd4);
       // byte t: weights of nodes 0..t (<= 16); two shift-adds, not a quarter-rate multiply
       const uint32_t pref1 = w4 + (w4 << 8);
       const uint32_t pref = pref1 + (pref1 << 16);
@@ -1424,6 +1463,7 @@ __device__ __forceinline__ void grid16_body(const FwRunParams& p) {
           if (mine && wn != wo) lds_add(gsum + (h.x >> 7), (wn - wo) << (16 * ((h.x >> 6) & 1)));
         }
         lds_order();
+        read_lvl1();  // the next iteration's level-1 words, behind the commit (in order)
         uint32_t dl = commit_me && mine ? wn - wo : 0u;
         dl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)dl, 0x111, 0xF, 0xF, true);
         dl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)dl, 0x112, 0xF, 0xF, true);
@@ -1504,6 +1544,7 @@ __device__ __forceinline__ void grid16_body(const FwRunParams& p) {
         }
       }
       lds_order();
+      read_lvl1();  // the next iteration's level-1 words, behind the commit (in order)
       // lanes 0..4 hold the changes: a 3-step row_shr scan leaves their sum on lane 4
       uint32_t dl = accepted && mine ? wn - wo : 0u;
       dl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)dl, 0x111, 0xF, 0xF, true);
@@ -1599,7 +1640,7 @@ __device__ __forceinline__ void grid16_body(const FwRunParams& p) {
           case 3: w0 = o0 + n_bfsn; w1 = o1 + n_bfsd; break;
           case 4: w0 = o0 + n_sdeg; w1 = o1 + n_adeg; break;
           case 5: w0 = o0 + n_bchg; w1 = o1 + yinc; break;
-          case 6: w0 = (uint64_t)sum_cut; w1 = (uint64_t)sum_bnodes; break;
+          case 6: w0 = o0 + s_cut; w1 = o1 + s_bn; break;
           case 7:
             w0 = (uint64_t)__double_as_longlong(sum_invb);
             w1 = (uint64_t)(uint32_t)cut | ((uint64_t)(uint32_t)bnodes << 32);
@@ -1630,10 +1671,10 @@ __device__ __forceinline__ void grid16_body(const FwRunParams& p) {
 // C3 +0.8%, +2% at 15,000-35,000 steps, profiles/r06/ab/ab_*_v6.jsonl) and a second lean
 // one (W2) keeps every register, at 2 waves per SIMD, for launches with no more than 2
 // waves of work per SIMD (the 8-GPU job's 8,192-chain shards: +4.6%).
-template <int LB, int MODE, int PER, bool FULL, bool BIG>
+template <int LB, int MODE, int PER, bool FULL, bool BIG, bool W4 = false>
 __global__ __launch_bounds__(64 * MAX_NW) __attribute__((amdgpu_waves_per_eu(3))) void fw_grid16_kernel(FwRunParams p) {
   static_assert(!FULL, "FULL instantiations: fw_grid16_full_kernel");
-  grid16_body<LB, MODE, PER, FULL, BIG, 1>(p);
+  grid16_body<LB, MODE, PER, FULL, BIG, 1, false, W4>(p);
 }
 // FULL (optional features on): the compiler's own register budget, as in round 5 (held to 3
 // waves per SIMD it spilled 130-190 B per lane)
@@ -1641,9 +1682,9 @@ template <int LB, int MODE, int PER, bool FULL, bool BIG>
 __global__ __launch_bounds__(64 * MAX_NW) void fw_grid16_full_kernel(FwRunParams p) {
   grid16_body<LB, MODE, PER, true, BIG, 1>(p);
 }
-template <int LB, int MODE, int PER>
+template <int LB, int MODE, int PER, bool W4>
 __global__ __launch_bounds__(64 * MAX_NW) void fw_grid16_w2_kernel(FwRunParams p) {
-  grid16_body<LB, MODE, PER, false, false, 1, true>(p);
+  grid16_body<LB, MODE, PER, false, false, 1, true, W4>(p);
 }
 
 // speculative attempts: R rows per chain.  A 3-waves-per-SIMD register budget (168 VGPRs:
@@ -1664,27 +1705,35 @@ int per16(int G) { return G <= 16 * 2 ? 2 : G <= 16 * 4 ? 4 : G <= 16 * 10 ? 10 
 int per16_big(int G) { return (G + 15) / 16 <= 32 ? 2 : 4; }
 bool is_big(int G) { return G > 16 * 16; }
 
-template <int LB, int MODE, int PER, bool FULL, bool BIG>
+template <int LB, int MODE, int PER, bool FULL, bool BIG, bool W4 = false>
 void* k16() {
   if constexpr (FULL)
     return reinterpret_cast<void*>(&fw_grid16_full_kernel<LB, MODE, PER, true, BIG>);
   else
-    return reinterpret_cast<void*>(&fw_grid16_kernel<LB, MODE, PER, false, BIG>);
+    return reinterpret_cast<void*>(&fw_grid16_kernel<LB, MODE, PER, false, BIG, W4>);
 }
 
-// the small-grid lean instantiations (fw_grid16_lean.hip; the stamps build: here)
-template <int LB, int MODE>
-void* pick16_small_lean(int G) {
+// the small-grid lean instantiations (fw_grid16_lean.hip; the stamps build: here); W4: the
+// grid width is a multiple of 4 (2-bit labels only: the SWAR weights' short masks)
+template <int LB, int MODE, bool W4>
+void* pick16_small_lean_w(int G) {
   switch (per16(G)) {
-    case 2: return k16<LB, MODE, 2, false, false>();
-    case 4: return k16<LB, MODE, 4, false, false>();
-    case 10: return k16<LB, MODE, 10, false, false>();
-    default: return k16<LB, MODE, 16, false, false>();
+    case 2: return k16<LB, MODE, 2, false, false, W4>();
+    case 4: return k16<LB, MODE, 4, false, false, W4>();
+    case 10: return k16<LB, MODE, 10, false, false, W4>();
+    default: return k16<LB, MODE, 16, false, false, W4>();
   }
+}
+template <int LB, int MODE>
+void* pick16_small_lean(int G, bool w4) {
+  if constexpr (LB == 2) {
+    if (w4) return pick16_small_lean_w<LB, MODE, true>(G);
+  }
+  return pick16_small_lean_w<LB, MODE, false>(G);
 }
 
 template <int LB, int MODE, bool FULL>
-void* pick16(int G) {
+void* pick16(int G, bool w4) {
   if (is_big(G)) {
     if constexpr (LB == 4) {
       return nullptr;  // large grids take 2- or 3-bit labels
@@ -1705,21 +1754,21 @@ void* pick16(int G) {
     }
   } else {
 #if defined(FW_STAMPS)
-    return pick16_small_lean<LB, MODE>(G);
+    return pick16_small_lean<LB, MODE>(G, w4);
 #else
-    return fw_grid16_pick_lean(LB, MODE, G);  // fw_grid16_lean.hip
+    return fw_grid16_pick_lean(LB, MODE, G, w4);  // fw_grid16_lean.hip
 #endif
   }
 }
 
-template <int MODE>
+template <int MODE, bool W4>
 void* pick16_w2(int G) {
   if (is_big(G)) return nullptr;
   switch (per16(G)) {
-    case 2: return reinterpret_cast<void*>(&fw_grid16_w2_kernel<2, MODE, 2>);
-    case 4: return reinterpret_cast<void*>(&fw_grid16_w2_kernel<2, MODE, 4>);
-    case 10: return reinterpret_cast<void*>(&fw_grid16_w2_kernel<2, MODE, 10>);
-    default: return reinterpret_cast<void*>(&fw_grid16_w2_kernel<2, MODE, 16>);
+    case 2: return reinterpret_cast<void*>(&fw_grid16_w2_kernel<2, MODE, 2, W4>);
+    case 4: return reinterpret_cast<void*>(&fw_grid16_w2_kernel<2, MODE, 4, W4>);
+    case 10: return reinterpret_cast<void*>(&fw_grid16_w2_kernel<2, MODE, 10, W4>);
+    default: return reinterpret_cast<void*>(&fw_grid16_w2_kernel<2, MODE, 16, W4>);
   }
 }
 
@@ -1747,11 +1796,12 @@ void* pick16_spec_mode(const FwRunParams& p) {
 template <bool FULL>
 void* pick16_mode(const FwRunParams& p) {
   const bool cut = p.mode == FW_PROPOSE_CUTEDGE;
+  const bool w4 = p.g.gw % 4 == 0;
   if (p.lb == 2)
-    return cut ? pick16<2, FW_PROPOSE_CUTEDGE, FULL>(p.G) : pick16<2, FW_PROPOSE_PAIRS, FULL>(p.G);
+    return cut ? pick16<2, FW_PROPOSE_CUTEDGE, FULL>(p.G, w4) : pick16<2, FW_PROPOSE_PAIRS, FULL>(p.G, w4);
   if (p.lb == 3)
-    return cut ? pick16<3, FW_PROPOSE_CUTEDGE, FULL>(p.G) : pick16<3, FW_PROPOSE_PAIRS, FULL>(p.G);
-  return cut ? pick16<4, FW_PROPOSE_CUTEDGE, FULL>(p.G) : pick16<4, FW_PROPOSE_PAIRS, FULL>(p.G);
+    return cut ? pick16<3, FW_PROPOSE_CUTEDGE, FULL>(p.G, w4) : pick16<3, FW_PROPOSE_PAIRS, FULL>(p.G, w4);
+  return cut ? pick16<4, FW_PROPOSE_CUTEDGE, FULL>(p.G, w4) : pick16<4, FW_PROPOSE_PAIRS, FULL>(p.G, w4);
 }
 
 int round16i(int x) { return (x + 15) / 16 * 16; }
@@ -1761,16 +1811,17 @@ int round16i(int x) { return (x + 15) / 16 * 16; }
 // fw_grid16_w2.hip and fw_grid16_lean.hip include this file with FW_G16_W2_TU /
 // FW_G16_LEAN_TU and compile only their pickers' instantiations
 #if defined(FW_G16_W2_TU) || defined(FW_STAMPS)
-void* fw_grid16_pick_w2(int mode, int G) {
-  return mode == FW_PROPOSE_CUTEDGE ? pick16_w2<FW_PROPOSE_CUTEDGE>(G) : pick16_w2<FW_PROPOSE_PAIRS>(G);
+void* fw_grid16_pick_w2(int mode, int G, bool w4) {
+  if (w4) return mode == FW_PROPOSE_CUTEDGE ? pick16_w2<FW_PROPOSE_CUTEDGE, true>(G) : pick16_w2<FW_PROPOSE_PAIRS, true>(G);
+  return mode == FW_PROPOSE_CUTEDGE ? pick16_w2<FW_PROPOSE_CUTEDGE, false>(G) : pick16_w2<FW_PROPOSE_PAIRS, false>(G);
 }
 #endif
 #if defined(FW_G16_LEAN_TU) || defined(FW_STAMPS)
-void* fw_grid16_pick_lean(int lb, int mode, int G) {
+void* fw_grid16_pick_lean(int lb, int mode, int G, bool w4) {
   const bool cut = mode == FW_PROPOSE_CUTEDGE;
   if (is_big(G)) return nullptr;  // fw_grid16.hip's large-grid plan
-  if (lb == 2) return cut ? pick16_small_lean<2, FW_PROPOSE_CUTEDGE>(G) : pick16_small_lean<2, FW_PROPOSE_PAIRS>(G);
-  if (lb == 4) return cut ? pick16_small_lean<4, FW_PROPOSE_CUTEDGE>(G) : pick16_small_lean<4, FW_PROPOSE_PAIRS>(G);
+  if (lb == 2) return cut ? pick16_small_lean<2, FW_PROPOSE_CUTEDGE>(G, w4) : pick16_small_lean<2, FW_PROPOSE_PAIRS>(G, w4);
+  if (lb == 4) return cut ? pick16_small_lean<4, FW_PROPOSE_CUTEDGE>(G, w4) : pick16_small_lean<4, FW_PROPOSE_PAIRS>(G, w4);
   return nullptr;
 }
 #endif
@@ -1829,7 +1880,7 @@ int fw_grid16_launch_nw(const FwRunParams& p) { return p.nw * fw_grid16_launch_r
 // the W2 instantiation (2-bit labels, small grids, lean, R = 1)
 static void* grid16_fn_w2(const FwRunParams& p) {
   if (p.lb != 2) return nullptr;
-  return fw_grid16_pick_w2(p.mode, p.G);
+  return fw_grid16_pick_w2(p.mode, p.G, p.g.gw % 4 == 0);
 }
 
 static void* grid16_fn_r(const FwRunParams& p, bool full, int R) {
@@ -2001,9 +2052,10 @@ int fw_grid16_plan(FwRunParams& p, int device, int* grid) {
   }
   const char* verbose = getenv("FLIPWALK_VERBOSE");
   if (verbose && verbose[0] == '1')
-    fprintf(stderr, "flipwalk: grid kernel %s%s, %d-bit labels, %d row(s) per chain, LDS %d B per "
+    fprintf(stderr, "flipwalk: grid kernel %s%s%s, %d-bit labels, %d row(s) per chain, LDS %d B per "
             "workgroup of %d waves, %d workgroups (%d chains) per CU\n",
             is_big(p.G) ? "large-grid plan" : "small-grid plan", p.w2 ? " (W2 register budget)" : "",
+            !big && !full && best_r == 1 && p.lb == 2 && p.g.gw % 4 == 0 ? " (W4 masks)" : "",
             p.lb, best_r, best_lds, best_nw, best_blocks, best_blocks * best_nw * cpw);
   const long long per_wg = (long long)cpw * best_nw;
   long long gsz = (long long)best_blocks * prop.multiProcessorCount;
