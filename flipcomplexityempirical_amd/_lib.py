@@ -25,6 +25,8 @@ MAP_SUM, MAP_FINALIZE = 1, 2
 ACCEPT_CUT, ACCEPT_BRATIO, ACCEPT_BOUNDARY = 0, 1, 2
 SERIES_CUT, SERIES_BNODES, SERIES_RUNG, SERIES_BY_RUNG = 0, 1, 2, 4
 SERIES_MAX_LAG = 1023
+TALLY_SUMS, TALLY_SEATS, TALLY_HIST = 0, 1, 2
+TALLY_MAX_COLS, TALLY_MAX_ELECTIONS = 8, 4
 
 STATS_DTYPE = np.dtype(
     [
@@ -101,6 +103,13 @@ SIGNATURES = [
     ("fw_chains_read_series", ctypes.c_int, [_P, _I32, _I64, _I64, _P, ctypes.c_size_t]),
     ("fw_chains_write_series", ctypes.c_int, [_P, _I32, _I64, _I64, _P, ctypes.c_size_t]),
     ("fw_chains_series_acf", ctypes.c_int, [_P, _I32, _I64, _I64, _I32, _P, _P]),
+    ("fw_chains_set_columns", ctypes.c_int, [_P, _P, _I32]),
+    ("fw_chains_set_elections", ctypes.c_int, [_P, _P, _I32]),
+    ("fw_chains_tally_async", ctypes.c_int, [_P]),
+    ("fw_chains_read_tally", ctypes.c_int, [_P, _I32, _P, ctypes.c_size_t]),
+    ("fw_chains_write_tally", ctypes.c_int, [_P, _I32, _P, ctypes.c_size_t]),
+    ("fw_chains_tally_reset", ctypes.c_int, [_P]),
+    ("fw_chains_tally_info", ctypes.c_int, [_P, _P]),
     ("fw_chains_read_map", ctypes.c_int, [_P, _I32, _I32, _I32, _I32, _P, ctypes.c_size_t]),
     ("fw_eval_flips", ctypes.c_int,
      [_P, _P, _I32, _P, _P, _I32, _I64, _I64, _P, _P, _P, _P]),

@@ -236,6 +236,10 @@ class Chains:
         # enable_series: the capacity and, per sample, the ladder epoch of its rung row (a
         # mirror of the handle's stamps, which a checkpoint carries as a validity mask)
         self.series_capacity, self._series_epoch = 0, None
+        # set_columns / set_elections: what a checkpoint carries of the tally besides the
+        # histogram; _tally_base is the n_tallied a restored checkpoint started from
+        self.columns, self.column_names, self.elections = None, None, None
+        self._tally_base = 0
         h = _lib.ctypes.c_void_p()
         check(L.fw_chains_create(dgraph.handle, self.n_chains, self.k, ptr(lab), per_chain,
                                  self.mode, self.pop_lo, self.pop_hi, ptr(self.thr), thr_per,
@@ -366,18 +370,22 @@ class Chains:
                                    _lib.RUNG_STATS_DTYPE))
 
     def run_tempered(self, steps_per_round: int, n_rounds: int, round0: Optional[int] = None,
-                     max_retries: int = DEFAULT_MAX_RETRIES, record: bool = False) -> None:
+                     max_retries: int = DEFAULT_MAX_RETRIES, record: bool = False,
+                     tally: bool = False) -> None:
         """``n_rounds`` x (``steps_per_round`` steps, one exchange), enqueued back to back and
         waited for once.  Rounds are numbered from ``round0`` (default: where the last call
         stopped, ``ladder_round``), which fixes the parity and the draws of each exchange.
         With ``record`` every round is run, record, exchange: a series sample carries the rung
-        its chain has just run on."""
+        its chain has just run on; with ``tally`` every round is run, tally, exchange, so a
+        plan is counted under that rung too."""
         if self.ladder_bases is None:
             raise ValueError("run_tempered needs a ladder (set_ladder)")
         r0 = self.ladder_round if round0 is None else int(round0)
         L = _lib.load()
         for i in range(int(n_rounds)):
             check(L.fw_chains_run_async(self._h, int(steps_per_round), int(max_retries)))
+            if tally:
+                self.tally()
             if record:
                 self.record()
             check(L.fw_chains_exchange_async(self._h, r0 + i))
@@ -464,14 +472,99 @@ class Chains:
         return (pooled, ps) if per_series else pooled
 
     def run_sampled(self, steps_per_sample: int, n_samples: int,
-                    max_retries: int = DEFAULT_MAX_RETRIES) -> None:
+                    max_retries: int = DEFAULT_MAX_RETRIES, tally: bool = False) -> None:
         """``n_samples`` x (``steps_per_sample`` steps, one recorded sample), enqueued back to
-        back and waited for once."""
+        back and waited for once.  With ``tally`` every sample's plans are tallied as well."""
         L = _lib.load()
         for _ in range(int(n_samples)):
             check(L.fw_chains_run_async(self._h, int(steps_per_sample), int(max_retries)))
+            if tally:
+                self.tally()
             self.record()
         self.sync()
+
+    # ------------------------------------------------------------- district tallies
+    def set_columns(self, cols) -> None:
+        """Node columns to sum per district (fw_chains_set_columns): an integer array
+        [n_cols, n] (or [n] for one column), or a dict name -> [n] whose insertion order
+        gives the column indices and whose names are kept in ``column_names``.  1 to 8
+        columns, values >= 0, every column's total below 2^31.  Replaces earlier columns,
+        drops the elections and zeroes the seat histogram."""
+        names = None
+        if isinstance(cols, dict):
+            names = [str(name) for name in cols]
+            if not names:
+                raise ValueError("no columns given")
+            cols = [np.asarray(v) for v in cols.values()]
+            if any(c.shape != (self.dgraph.n,) for c in cols):
+                raise ValueError(f"every column must be [{self.dgraph.n}]")
+            cols = np.stack(cols)
+        a = np.asarray(cols)
+        if a.dtype.kind not in "iub":
+            raise ValueError(f"columns must be integers, got {a.dtype}")
+        if a.dtype.kind == "u" and a.size and int(a.max()) >= 2 ** 63:
+            raise ValueError("column value outside int64")
+        a = np.ascontiguousarray(np.atleast_2d(a), np.int64)
+        if a.ndim != 2 or a.shape[1] != self.dgraph.n:
+            raise ValueError(f"columns must be [n_cols, {self.dgraph.n}], got {a.shape}")
+        check(_lib.load().fw_chains_set_columns(self._h, ptr(a), a.shape[0]))
+        self.columns, self.column_names = a, names
+        self.elections = np.zeros((0, 2), np.int32)
+
+    def _column_index(self, c) -> int:
+        if isinstance(c, str):
+            if not self.column_names or c not in self.column_names:
+                raise ValueError(f"no column named {c!r}")
+            return self.column_names.index(c)
+        return int(c)
+
+    def set_elections(self, pairs) -> None:
+        """Elections between two columns each (fw_chains_set_elections): up to 4 pairs
+        (a, b) of distinct column indices or names.  Zeroes the seat histogram."""
+        ab = np.array([[self._column_index(a), self._column_index(b)] for a, b in pairs],
+                      np.int32).reshape(-1, 2)
+        ab = np.ascontiguousarray(ab)
+        check(_lib.load().fw_chains_set_elections(self._h, ptr(ab) if len(ab) else None,
+                                                  len(ab)))
+        self.elections = ab
+
+    def tally(self) -> None:
+        """Tally every chain's current plan on the handle's stream, behind the runs already
+        there (fw_chains_tally_async); no wait."""
+        check(_lib.load().fw_chains_tally_async(self._h))
+
+    def tally_info(self) -> dict:
+        info = np.zeros(5, np.int64)
+        check(_lib.load().fw_chains_tally_info(self._h, ptr(info)))
+        return {"n_cols": int(info[0]), "n_elections": int(info[1]), "label_bits": int(info[2]),
+                "n_groups": int(info[3]), "n_tallied": int(info[4]) + self._tally_base}
+
+    def _read_tally(self, what, arr):
+        check(_lib.load().fw_chains_read_tally(self._h, what, ptr(arr) if arr.size else None,
+                                               arr.nbytes))
+        return arr
+
+    def tallies(self) -> np.ndarray:
+        """int64 [n_chains, n_cols, k]: the district sums of every column, last tally."""
+        n_cols = self.tally_info()["n_cols"]
+        return self._read_tally(_lib.TALLY_SUMS, np.empty((self.n_chains, n_cols, self.k), np.int64))
+
+    def seats(self) -> np.ndarray:
+        """int32 [n_chains, n_elections, 2]: {districts the first column wins outright,
+        districts tied} of the last tally."""
+        n_el = self.tally_info()["n_elections"]
+        return self._read_tally(_lib.TALLY_SEATS, np.empty((self.n_chains, n_el, 2), np.int32))
+
+    def seat_hist(self) -> np.ndarray:
+        """uint64 [n_groups, n_elections, k + 1]: tallied plans per seat count of the first
+        column, over all tallies; one group, or one per rung under a ladder."""
+        info = self.tally_info()
+        return self._read_tally(_lib.TALLY_HIST, np.empty(
+            (info["n_groups"], info["n_elections"], self.k + 1), np.uint64))
+
+    def tally_reset(self) -> None:
+        check(_lib.load().fw_chains_tally_reset(self._h))
+        self._tally_base = 0
 
     # ------------------------------------------------------------- sampled waits
     def enable_sampled_waits(self) -> None:
@@ -555,6 +648,12 @@ class Chains:
             # which samples' rung rows belong to the current ladder (the by-rung view)
             ck["series_valid"] = ((self._series_epoch[:info["n_samples"]] == info["epoch"]) &
                                   (info["epoch"] > 0))
+        if self.columns is not None:
+            ck["tally_columns"], ck["tally_elections"] = self.columns, self.elections
+            if self.column_names is not None:
+                ck["tally_names"] = np.array(self.column_names, dtype=np.str_)
+            ck["tally_hist"] = self.seat_hist()
+            ck["n_tallied"] = np.int64(self.tally_info()["n_tallied"])
         return ck
 
     def restore(self, ck: dict) -> None:
@@ -632,6 +731,21 @@ class Chains:
                 edges = np.flatnonzero(np.diff(np.r_[False, valid, False].astype(np.int8)))
                 for lo, hi in zip(edges[::2], edges[1::2]):
                     self.write_series("rung", ck["series_rung"][lo:hi], t0=int(lo))
+        # the tally after the ladder as well: set_ladder zeroes the seat histogram, whose
+        # shape follows the rung count
+        if "tally_columns" in ck:
+            cols = np.asarray(ck["tally_columns"])
+            if "tally_names" in ck:
+                cols = {str(name): col for name, col in zip(ck["tally_names"], cols)}
+            self.set_columns(cols)
+            self.set_elections(np.asarray(ck["tally_elections"], np.int32).reshape(-1, 2))
+            hist = np.ascontiguousarray(ck["tally_hist"], np.uint64)
+            if hist.shape != self.seat_hist().shape:
+                raise ValueError("checkpoint of another seat histogram shape")
+            check(L.fw_chains_write_tally(self._h, _lib.TALLY_HIST,
+                                          ptr(hist) if hist.size else None, hist.nbytes))
+            self._tally_base = int(ck["n_tallied"]) - (self.tally_info()["n_tallied"] -
+                                                       self._tally_base)
 
     def save_checkpoint(self, path: str) -> None:
         ck = self.checkpoint()

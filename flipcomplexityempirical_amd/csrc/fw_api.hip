@@ -195,6 +195,15 @@ struct fw_chains {
   int32_t* d_ser_bn = nullptr;
   int32_t* d_ser_rung = nullptr;       // allocated on the first rung row (all -1 before it)
   std::vector<int64_t> ser_epoch;      // [ser_cap] ladder epoch each sample's rung row belongs to
+  // fw_chains_set_columns (tal_cols == 0: none); FwTallyParams / FwSeatsParams name the arrays
+  int32_t tal_cols = 0, tal_el = 0;
+  int32_t tal_ab[FW_TALLY_MAX_EL][2] = {};
+  int64_t n_tallied = 0;
+  bool tal_have_sums = false, tal_have_seats = false;  // a tally ran since the columns / elections
+  uint32_t* d_tal_cols = nullptr;
+  int64_t* d_tal_sums = nullptr;
+  int32_t* d_tal_seats = nullptr;            // [n_chains][FW_TALLY_MAX_EL][2] (n_el rows in use)
+  unsigned long long* d_tal_hist = nullptr;  // room for 64 groups x 4 elections x (k + 1) bins
 };
 
 namespace {
@@ -286,6 +295,12 @@ bool plan_valid(const fw_graph* g, const int16_t* lab, int k, int64_t lo, int64_
 }
 
 size_t ring_bins(int r) { return (size_t)r * (size_t)r + 1; }
+
+// the seat histogram's buffer: the largest [groups][elections][k + 1] a handle of k districts
+// can ask for, so neither fw_chains_set_elections nor fw_chains_set_ladder reallocates it
+size_t tally_hist_bytes(int k) {
+  return sizeof(unsigned long long) * FW_TALLY_MAX_GROUPS * FW_TALLY_MAX_EL * (size_t)(k + 1);
+}
 
 // first two cut ring edges of a plan in ring order: out = {i, j} (-1, -1 if fewer than two)
 void ring_pair_of(const fw_chains* c, const int16_t* lab, int32_t* out) {
@@ -500,7 +515,8 @@ void fw_chains_destroy(fw_chains* c) {
                   c->d_ring,   c->d_ring_node, c->d_hist_ring, c->d_gscr, c->d_segdone,
                   c->d_wsamp,  c->d_wlp,   c->d_lad_thr, c->d_lad_thr53, c->d_logb, c->d_rung,
                   c->d_chain_of, c->d_gmin, c->d_snap, c->d_rstats,
-                  c->d_ser_cut, c->d_ser_bn, c->d_ser_rung};
+                  c->d_ser_cut, c->d_ser_bn, c->d_ser_rung,
+                  c->d_tal_cols, c->d_tal_sums, c->d_tal_seats, c->d_tal_hist};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -1322,6 +1338,8 @@ int fw_chains_set_ladder(fw_chains* c, const double* thr_rows, const double* log
   c->n_rungs = n_rungs;
   c->lad_set.assign(set_of_chain, set_of_chain + C);
   c->lad_epoch += 1;  // series samples recorded so far belong to the previous ladder
+  if (c->d_tal_hist)  // the seat histogram is kept by rung: its group count has changed
+    HIPCHK(hipMemset(c->d_tal_hist, 0, tally_hist_bytes(c->k)));
   return ladder_snapshot(c, st.data());
 }
 
@@ -1663,6 +1681,199 @@ int fw_chains_series_acf(fw_chains* c, int32_t what, int64_t t0, int64_t n, int3
   if (d_pool) (void)hipFree(d_pool);
   if (tmp) (void)hipFree(tmp);
   return rc;
+}
+
+// ---------------------------------------------------------------- district tallies
+int fw_chains_set_columns(fw_chains* c, const int64_t* cols, int32_t n_cols) {
+  if (!c || !cols) return fail(FW_EINVAL, "fw_chains_set_columns: null");
+  if (n_cols < 1 || n_cols > FW_TALLY_MAX_COLS)
+    return fail(FW_EINVAL, "n_cols = %d outside [1, %d]", n_cols, FW_TALLY_MAX_COLS);
+  const size_t n = (size_t)c->g->n, C = (size_t)c->n_chains;
+  const int n_pairs = (n_cols + 1) / 2;
+  // device form: columns 2p and 2p + 1 side by side, [n_pairs][n][2] (fw_tally.hip)
+  std::vector<uint32_t> packed((size_t)n_pairs * n * 2, 0u);
+  for (int j = 0; j < n_cols; ++j) {
+    int64_t total = 0;
+    for (size_t x = 0; x < n; ++x) {
+      const int64_t v = cols[(size_t)j * n + x];
+      if (v < 0) return fail(FW_EINVAL, "column %d: value %lld at node %zu is negative", j,
+                             (long long)v, x);
+      // v >= 2^31 alone is already too much; below it the running total cannot overflow
+      if (v >= (1ll << 31) || (total += v) >= (1ll << 31))
+        return fail(FW_EINVAL, "column %d: the total over the nodes must stay below 2^31", j);
+      packed[((size_t)(j >> 1) * n + x) * 2 + (j & 1)] = (uint32_t)v;
+    }
+  }
+  HIPCHK(hipSetDevice(c->g->device));
+  HIPCHK(hipStreamSynchronize(c->stream));  // a tally in flight reads the old columns
+  // the new buffers first: on failure the handle keeps what it had
+  uint32_t* d_cols = nullptr;
+  int64_t* d_sums = nullptr;
+  int32_t* d_seats = c->d_tal_seats;
+  unsigned long long* d_hist = c->d_tal_hist;
+  bool ok = hipMalloc(&d_cols, sizeof(uint32_t) * packed.size()) == hipSuccess &&
+            hipMalloc(&d_sums, sizeof(int64_t) * C * n_cols * c->k) == hipSuccess &&
+            (d_seats || hipMalloc(&d_seats, sizeof(int32_t) * C * FW_TALLY_MAX_EL * 2) == hipSuccess) &&
+            (d_hist || hipMalloc(&d_hist, tally_hist_bytes(c->k)) == hipSuccess);
+  const bool up = ok &&
+                  hipMemcpy(d_cols, packed.data(), sizeof(uint32_t) * packed.size(),
+                            hipMemcpyHostToDevice) == hipSuccess &&
+                  hipMemset(d_hist, 0, tally_hist_bytes(c->k)) == hipSuccess;
+  if (!up) {
+    if (d_cols) (void)hipFree(d_cols);
+    if (d_sums) (void)hipFree(d_sums);
+    if (d_seats && !c->d_tal_seats) (void)hipFree(d_seats);
+    if (d_hist && !c->d_tal_hist) (void)hipFree(d_hist);
+    (void)hipGetLastError();
+    return ok ? fail(FW_EHIP, "column upload failed")
+              : fail(FW_ENOMEM, "%d columns for %d chains", n_cols, c->n_chains);
+  }
+  if (c->d_tal_cols) (void)hipFree(c->d_tal_cols);
+  if (c->d_tal_sums) (void)hipFree(c->d_tal_sums);
+  c->d_tal_cols = d_cols;
+  c->d_tal_sums = d_sums;
+  c->d_tal_seats = d_seats;
+  c->d_tal_hist = d_hist;
+  c->tal_cols = n_cols;
+  c->tal_el = 0;
+  c->tal_have_sums = c->tal_have_seats = false;
+  return FW_OK;
+}
+
+int fw_chains_set_elections(fw_chains* c, const int32_t* ab, int32_t n_el) {
+  if (!c || (!ab && n_el != 0)) return fail(FW_EINVAL, "fw_chains_set_elections: null");
+  if (n_el < 0 || n_el > FW_TALLY_MAX_EL)
+    return fail(FW_EINVAL, "n_el = %d outside [0, %d]", n_el, FW_TALLY_MAX_EL);
+  if (!c->tal_cols) return fail(FW_ESTATE, "fw_chains_set_elections: no columns are set");
+  for (int e = 0; e < n_el; ++e) {
+    const int a = ab[2 * e], b = ab[2 * e + 1];
+    if (a < 0 || a >= c->tal_cols || b < 0 || b >= c->tal_cols)
+      return fail(FW_EINVAL, "election %d: columns (%d, %d) outside [0, %d)", e, a, b, c->tal_cols);
+    if (a == b) return fail(FW_EINVAL, "election %d: both parties are column %d", e, a);
+  }
+  HIPCHK(hipSetDevice(c->g->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemset(c->d_tal_hist, 0, tally_hist_bytes(c->k)));
+  for (int e = 0; e < n_el; ++e) {
+    c->tal_ab[e][0] = ab[2 * e];
+    c->tal_ab[e][1] = ab[2 * e + 1];
+  }
+  c->tal_el = n_el;
+  c->tal_have_seats = false;
+  return FW_OK;
+}
+
+int fw_chains_tally_async(fw_chains* c) {
+  if (!c) return fail(FW_EINVAL, "null handle");
+  if (!c->tal_cols) return fail(FW_ESTATE, "fw_chains_tally_async: no columns are set");
+  HIPCHK(hipSetDevice(c->g->device));
+  FwTallyParams t{};
+  t.labels = c->d_labels;
+  t.lab_stride = c->p.lab_stride;
+  t.cols = c->d_tal_cols;
+  t.sums = c->d_tal_sums;
+  t.n_chains = c->n_chains;
+  t.n = c->g->n;
+  t.k = c->k;
+  t.lb = c->lb;
+  t.n_cols = c->tal_cols;
+  // like the exchange and record steps: the run timing events are left alone
+  int le = fw_launch_tally(t, c->stream);
+  if (le != 0) return fail(FW_EHIP, "tally launch failed: %s", hipGetErrorString((hipError_t)le));
+  c->tal_have_sums = true;
+  if (c->tal_el) {
+    FwSeatsParams s{};
+    s.sums = c->d_tal_sums;
+    s.rung = c->n_rungs ? c->d_rung : nullptr;
+    s.seats = c->d_tal_seats;
+    s.hist = c->d_tal_hist;
+    std::memcpy(s.ab, c->tal_ab, sizeof s.ab);
+    s.n_chains = c->n_chains;
+    s.k = c->k;
+    s.n_cols = c->tal_cols;
+    s.n_el = c->tal_el;
+    s.n_groups = c->n_rungs ? c->n_rungs : 1;
+    le = fw_launch_seats(s, c->stream);
+    if (le != 0) return fail(FW_EHIP, "seat launch failed: %s", hipGetErrorString((hipError_t)le));
+  }
+  c->tal_have_seats = true;
+  c->n_tallied += 1;
+  return FW_OK;
+}
+
+namespace {
+
+// bytes of a FW_TALLY_* array of the handle as it is configured now
+int tally_bytes(const fw_chains* c, int32_t what, size_t* need) {
+  const size_t C = (size_t)c->n_chains;
+  switch (what) {
+    case FW_TALLY_SUMS:
+      *need = sizeof(int64_t) * C * c->tal_cols * c->k;
+      return FW_OK;
+    case FW_TALLY_SEATS:
+      *need = sizeof(int32_t) * C * c->tal_el * 2;
+      return FW_OK;
+    case FW_TALLY_HIST:
+      *need = sizeof(uint64_t) * (size_t)(c->n_rungs ? c->n_rungs : 1) * c->tal_el * (c->k + 1);
+      return FW_OK;
+    default:
+      return fail(FW_EINVAL, "unknown tally kind %d", what);
+  }
+}
+
+}  // namespace
+
+int fw_chains_read_tally(fw_chains* c, int32_t what, void* dst, size_t bytes) {
+  if (!c) return fail(FW_EINVAL, "fw_chains_read_tally: null");
+  size_t need = 0;
+  if (const int rc = tally_bytes(c, what, &need)) return rc;
+  if (!c->tal_cols) return fail(FW_ESTATE, "fw_chains_read_tally: no columns are set");
+  if ((what == FW_TALLY_SUMS && !c->tal_have_sums) || (what == FW_TALLY_SEATS && !c->tal_have_seats))
+    return fail(FW_ESTATE, "fw_chains_read_tally: nothing has been tallied yet");
+  if (bytes < need || (!dst && need)) return fail(FW_EINVAL, "the tally needs %zu bytes", need);
+  HIPCHK(hipSetDevice(c->g->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (!need) return FW_OK;
+  const void* src = what == FW_TALLY_SUMS    ? (const void*)c->d_tal_sums
+                    : what == FW_TALLY_SEATS ? (const void*)c->d_tal_seats
+                                             : (const void*)c->d_tal_hist;
+  HIPCHK(hipMemcpy(dst, src, need, hipMemcpyDeviceToHost));
+  return FW_OK;
+}
+
+int fw_chains_write_tally(fw_chains* c, int32_t what, const void* src, size_t bytes) {
+  if (!c) return fail(FW_EINVAL, "fw_chains_write_tally: null");
+  if (what != FW_TALLY_HIST)
+    return fail(FW_EINVAL, "fw_chains_write_tally: only FW_TALLY_HIST can be written (got %d)", what);
+  if (!c->tal_cols) return fail(FW_ESTATE, "fw_chains_write_tally: no columns are set");
+  size_t need = 0;
+  if (const int rc = tally_bytes(c, what, &need)) return rc;
+  if (bytes < need || (!src && need)) return fail(FW_EINVAL, "the seat histogram needs %zu bytes", need);
+  HIPCHK(hipSetDevice(c->g->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (need) HIPCHK(hipMemcpy(c->d_tal_hist, src, need, hipMemcpyHostToDevice));
+  return FW_OK;
+}
+
+int fw_chains_tally_reset(fw_chains* c) {
+  if (!c) return fail(FW_EINVAL, "null handle");
+  if (c->d_tal_hist) {
+    HIPCHK(hipSetDevice(c->g->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemset(c->d_tal_hist, 0, tally_hist_bytes(c->k)));
+  }
+  c->n_tallied = 0;
+  return FW_OK;
+}
+
+int fw_chains_tally_info(const fw_chains* c, int64_t info[5]) {
+  if (!c || !info) return fail(FW_EINVAL, "fw_chains_tally_info: null");
+  info[0] = c->tal_cols;
+  info[1] = c->tal_el;
+  info[2] = c->lb;
+  info[3] = c->n_rungs ? c->n_rungs : 1;
+  info[4] = c->n_tallied;
+  return FW_OK;
 }
 
 int fw_chains_enable_ring(fw_chains* c, const int32_t* ring_u, const int32_t* ring_w,

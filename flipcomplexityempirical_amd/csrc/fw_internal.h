@@ -238,6 +238,40 @@ struct FwPoolParams {
   int64_t n;
 };
 
+// ---- district tallies of node columns (fw_chains_set_columns, fw_tally.hip) --------------
+#define FW_TALLY_MAX_COLS 8
+#define FW_TALLY_MAX_EL 4
+#define FW_TALLY_MAX_GROUPS 64  // rungs of a ladder (fw_chains_set_ladder)
+#define FW_TALLY_TILE 1024      // nodes of the columns staged in LDS at a time (a multiple of 64)
+#define FW_TALLY_NW_REG 16      // waves (chains) per workgroup, register accumulators (k <= 8)
+#define FW_TALLY_NW_BIN 8       // waves per workgroup with LDS bins (k <= 32; half of it above)
+#define FW_SEATS_LDS_BINS 2048  // seat histograms up to this many bins are summed in LDS first
+
+// fw_chains_tally_async: sums[c][j][d] = sum of column j over the nodes chain c labels d
+struct FwTallyParams {
+  const uint8_t* labels;  // packed lb-bit label records, chain c at labels + c * lab_stride
+  int64_t lab_stride;     // bytes, a multiple of 16
+  const uint32_t* cols;   // [ceil(n_cols / 2)][n][2]: columns 2p and 2p + 1 (zeros when absent)
+  int64_t* sums;          // [n_chains][n_cols][k]
+  int32_t n_chains, n, k, lb, n_cols;
+};
+
+// the seat step: seats[c][e] = {wins, ties} of election e = (ab[e][0], ab[e][1]) and
+// hist[g][e][wins] += 1, g = rung[c] (0 without a ladder)
+struct FwSeatsParams {
+  const int64_t* sums;       // [n_chains][n_cols][k]
+  const int32_t* rung;       // [n_chains] or null
+  int32_t* seats;            // [n_chains][n_el][2]
+  unsigned long long* hist;  // [n_groups][n_el][k + 1]
+  int32_t ab[FW_TALLY_MAX_EL][2];
+  int32_t n_chains, k, n_cols, n_el, n_groups;
+};
+
+// Host-side launchers implemented in fw_tally.hip.
+void fw_tally_plan(int k, int lb, int* nw, int* lds_bytes);
+int fw_launch_tally(const FwTallyParams& t, void* stream);
+int fw_launch_seats(const FwSeatsParams& s, void* stream);
+
 // Host-side launchers implemented in fw_series.hip.
 int fw_launch_record(const FwRecordParams& r, void* stream);
 int fw_launch_regroup(const FwRegroupParams& r, void* stream);

@@ -74,6 +74,31 @@ class Graph:
     def pop_array(self) -> np.ndarray:
         return np.ones(self.n, np.int64) if self.pop is None else self.pop
 
+    def columns(self, names: Sequence[str]) -> np.ndarray:
+        """int64 [len(names), n]: node attributes as tally columns (``Chains.set_columns``),
+        cast as ``from_json`` casts TOTPOP (``int()`` of a str; an integral float is taken
+        too).  ValueError for a missing or non-integral attribute."""
+        if isinstance(names, str):
+            names = [names]
+        if self.node_attrs is None:
+            raise ValueError("the graph carries no node attributes")
+        out = np.empty((len(names), self.n), np.int64)
+        for j, name in enumerate(names):
+            for x, attrs in enumerate(self.node_attrs):
+                node = self.nodes[x] if self.nodes else x
+                if name not in attrs:
+                    raise ValueError(f"node {node!r} has no attribute {name!r}")
+                v = attrs[name]
+                try:
+                    if isinstance(v, (bool, np.bool_)) or (
+                            isinstance(v, (float, np.floating)) and not float(v).is_integer()):
+                        raise ValueError
+                    out[j, x] = int(v)
+                except (TypeError, ValueError, OverflowError):
+                    raise ValueError(f"attribute {name!r} of node {node!r} is not an "
+                                     f"integer: {v!r}") from None
+        return out
+
     def validate(self) -> None:
         rp, col = self.rowptr, self.col
         if rp[0] != 0 or rp[-1] != len(col) or np.any(np.diff(rp) < 0):

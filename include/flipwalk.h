@@ -164,13 +164,13 @@ const char* fw_last_error(void);
 /* Library/ABI version, e.g. 0x000600 for 0.6.0 (0.2: spatial maps; 0.3: bound
  * schedules; 0.4: ring observable, checkpoint/resume; 0.5: sampled geometric waits;
  * 0.6: fw_chains_launch_info; 0.7: fw_build_info; the ladder entry points
- * fw_chains_set_ladder / fw_chains_exchange_async and the observable-series entry points
- * arrived in 0.7 without a bump). */
+ * fw_chains_set_ladder / fw_chains_exchange_async, the observable-series entry points and
+ * the tally entry points arrived in 0.7 without a bump). */
 int32_t fw_version(void);
 
 /* Provenance of this build (static string, never NULL): "src=<sha256 of the flip
  * kernels, headers and ABI source> flags=<compiler flags, including any -D>
- * series=<sha256 of fw_series.hip>".  Bench lines and PMC
+ * series=<sha256 of fw_series.hip> tally=<sha256 of fw_tally.hip>".  Bench lines and PMC
  * profiles carry it, so a measurement names the code it measured. */
 const char* fw_build_info(void);
 
@@ -410,6 +410,56 @@ int fw_chains_write_series(fw_chains* c, int32_t what, int64_t t0, int64_t n, co
                            size_t bytes);
 int fw_chains_series_acf(fw_chains* c, int32_t what, int64_t t0, int64_t n, int32_t max_lag,
                          int64_t* per_series, double* pooled);
+
+/* ---- district tallies of node columns and seat counts ---------------------------------
+ * The reference gives every node vote columns (pink / purple, grid_chain_sec11.py:223) and
+ * imports Election, mean_median and efficiency_gap; its census graphs carry many columns
+ * besides TOTPOP.  A tally sums node columns per district over every chain's current plan, on
+ * the device and between launches, as the exchange and record steps are placed; no run kernel
+ * changes.  Every result is an exact integer.
+ *
+ * fw_chains_set_columns: cols int64 [n_cols][n], 1 <= n_cols <= 8, every value >= 0 and every
+ * column's total over the nodes < 2^31 (so a district sum fits 32 bits; the device keeps the
+ * columns as 32-bit values), else FW_EINVAL, checked on the host before the device is touched.
+ * May be repeated: it replaces the columns, drops the elections and zeroes the seat histogram.
+ *
+ * fw_chains_set_elections: ab int32 [n_el][2], 0 <= n_el <= 4 (ab may be NULL when n_el is 0),
+ * each entry a pair (a, b) of distinct column indices (FW_EINVAL); FW_ESTATE without columns.
+ * Zeroes the seat histogram.
+ *
+ * fw_chains_tally_async (FW_ESTATE without columns) enqueues on the handle's stream, with no
+ * host synchronisation and without touching fw_chains_last_kernel_ms, the tally of every
+ * chain's current plan (stuck chains like any other):
+ *   T[c][j][d]  = sum of column j over the nodes that chain c labels d
+ *   wins[c][e]  = #{d : T[c][a][d] > T[c][b][d]} (strict),  ties[c][e] = #{d : T[c][a][d] ==
+ *                 T[c][b][d]}   for election e = (a, b)
+ *   seat_hist[g][e][wins[c][e]] += 1, g = the chain's current rung under a ladder, else 0.
+ * The host counter n_tallied is incremented at enqueue.  T and {wins, ties} are plain vector
+ * stores from one owner each (no atomics, no dependence on thread order); the seat histogram
+ * is accumulated with integer atomics, whose sum does not depend on the order.
+ *
+ * fw_chains_read_tally synchronises, then copies
+ *   FW_TALLY_SUMS   int64  [n_chains][n_cols][k]       of the last tally
+ *   FW_TALLY_SEATS  int32  [n_chains][n_el][2]         {wins, ties} of the last tally
+ *   FW_TALLY_HIST   uint64 [n_groups][n_el][k + 1]     accumulated over all tallies;
+ *                                                      n_groups = n_rungs, or 1 without a ladder
+ * FW_ESTATE without columns, and for SUMS / SEATS when nothing was tallied since the columns
+ * (SEATS: the elections) were set.  fw_chains_write_tally restores FW_TALLY_HIST (checkpoints;
+ * n_tallied is not changed); fw_chains_tally_reset zeroes the histogram and n_tallied.
+ * fw_chains_tally_info: info = {n_cols, n_el, label bits per node of the handle's plans,
+ * n_groups, n_tallied}.  fw_chains_reset_observables leaves all of this alone, as it leaves
+ * the series alone; fw_chains_set_ladder zeroes the histogram, because its group count changes.
+ * (These entry points arrived in 0.7 without a version bump.) */
+#define FW_TALLY_SUMS 0
+#define FW_TALLY_SEATS 1
+#define FW_TALLY_HIST 2
+int fw_chains_set_columns(fw_chains* c, const int64_t* cols /*[n_cols][n]*/, int32_t n_cols);
+int fw_chains_set_elections(fw_chains* c, const int32_t* ab /*[n_el][2]*/, int32_t n_el);
+int fw_chains_tally_async(fw_chains* c);
+int fw_chains_read_tally(fw_chains* c, int32_t what, void* dst, size_t bytes);
+int fw_chains_write_tally(fw_chains* c, int32_t what, const void* src, size_t bytes);
+int fw_chains_tally_reset(fw_chains* c);
+int fw_chains_tally_info(const fw_chains* c, int64_t info[5]);
 
 /* Read a map (FW_MAP_*) of chains [chain0, chain0 + n_chains) as int64
  * [n_chains][len], or with FW_MAP_SUM its sum over those chains [len]; len is
