@@ -27,6 +27,7 @@ SERIES_CUT, SERIES_BNODES, SERIES_RUNG, SERIES_BY_RUNG = 0, 1, 2, 4
 SERIES_MAX_LAG = 1023
 TALLY_SUMS, TALLY_SEATS, TALLY_HIST = 0, 1, 2
 TALLY_MAX_COLS, TALLY_MAX_ELECTIONS = 8, 4
+GEOM_DISTRICTS, GEOM_HIST = 0, 1
 
 STATS_DTYPE = np.dtype(
     [
@@ -110,6 +111,12 @@ SIGNATURES = [
     ("fw_chains_write_tally", ctypes.c_int, [_P, _I32, _P, ctypes.c_size_t]),
     ("fw_chains_tally_reset", ctypes.c_int, [_P]),
     ("fw_chains_tally_info", ctypes.c_int, [_P, _P]),
+    ("fw_chains_set_geometry", ctypes.c_int, [_P, _P, _P, _P]),
+    ("fw_chains_geometry_async", ctypes.c_int, [_P]),
+    ("fw_chains_read_geometry", ctypes.c_int, [_P, _I32, _P, ctypes.c_size_t]),
+    ("fw_chains_write_geometry", ctypes.c_int, [_P, _I32, _P, ctypes.c_size_t]),
+    ("fw_chains_geometry_reset", ctypes.c_int, [_P]),
+    ("fw_chains_geometry_info", ctypes.c_int, [_P, _P]),
     ("fw_chains_read_map", ctypes.c_int, [_P, _I32, _I32, _I32, _I32, _P, ctypes.c_size_t]),
     ("fw_eval_flips", ctypes.c_int,
      [_P, _P, _I32, _P, _P, _I32, _I64, _I64, _P, _P, _P, _P]),

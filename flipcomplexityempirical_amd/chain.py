@@ -122,6 +122,31 @@ def check_ladder_layout(n_chains: int, n_rungs: int, set_of_chain, rung_of_chain
     return s, r
 
 
+def check_geometry_arrays(n: int, n_edges: int, edge_weights=None, area=None, exterior=None):
+    """fw_chains_set_geometry's host validation (ValueError instead of FW_EINVAL), before the
+    library is called: each array is None or integers of shape [n_edges] (``edge_weights``) or
+    [n] (``area``, ``exterior``), every value >= 0 and every total below 2^31.  Returns the
+    three as contiguous int64 arrays (or None)."""
+    out = []
+    for name, a, length in (("edge_weights", edge_weights, n_edges), ("area", area, n),
+                            ("exterior", exterior, n)):
+        if a is None:
+            out.append(None)
+            continue
+        a = np.asarray(a)
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"{name} must be integers, got {a.dtype} "
+                             "(compactness.quantise turns lengths and areas into them)")
+        if a.shape != (int(length),):
+            raise ValueError(f"{name} must be [{int(length)}], got {a.shape}")
+        if a.size and int(a.min()) < 0:
+            raise ValueError(f"{name} must be >= 0")
+        if a.size and (int(a.max()) >= 2 ** 31 or int(a.astype(np.uint64).sum()) >= 2 ** 31):
+            raise ValueError(f"the total of {name} must stay below 2^31")
+        out.append(np.ascontiguousarray(a, np.int64))
+    return tuple(out)
+
+
 def expected_wait_sum(stats, n_nodes: int, k: int) -> np.ndarray:
     """Σ_t E[geom_wait_t] = (N^k - 1) * Σ 1/|B_t| - T (geom_wait, grid_chain_sec11.py:147-148)."""
     M = float(n_nodes ** k - 1)
@@ -240,6 +265,10 @@ class Chains:
         # histogram; _tally_base is the n_tallied a restored checkpoint started from
         self.columns, self.column_names, self.elections = None, None, None
         self._tally_base = 0
+        # set_geometry: the three arrays a checkpoint carries (None: unit weights, unit areas,
+        # no exterior); _geometry_base as _tally_base
+        self.geometry_arrays = None
+        self._geometry_base = 0
         h = _lib.ctypes.c_void_p()
         check(L.fw_chains_create(dgraph.handle, self.n_chains, self.k, ptr(lab), per_chain,
                                  self.mode, self.pop_lo, self.pop_hi, ptr(self.thr), thr_per,
@@ -371,13 +400,14 @@ class Chains:
 
     def run_tempered(self, steps_per_round: int, n_rounds: int, round0: Optional[int] = None,
                      max_retries: int = DEFAULT_MAX_RETRIES, record: bool = False,
-                     tally: bool = False) -> None:
+                     tally: bool = False, geometry: bool = False) -> None:
         """``n_rounds`` x (``steps_per_round`` steps, one exchange), enqueued back to back and
         waited for once.  Rounds are numbered from ``round0`` (default: where the last call
         stopped, ``ladder_round``), which fixes the parity and the draws of each exchange.
         With ``record`` every round is run, record, exchange: a series sample carries the rung
         its chain has just run on; with ``tally`` every round is run, tally, exchange, so a
-        plan is counted under that rung too."""
+        plan is counted under that rung too, and with ``geometry`` its districts are measured
+        under it (run, tally, geometry, record, exchange)."""
         if self.ladder_bases is None:
             raise ValueError("run_tempered needs a ladder (set_ladder)")
         r0 = self.ladder_round if round0 is None else int(round0)
@@ -386,6 +416,8 @@ class Chains:
             check(L.fw_chains_run_async(self._h, int(steps_per_round), int(max_retries)))
             if tally:
                 self.tally()
+            if geometry:
+                self.geometry()
             if record:
                 self.record()
             check(L.fw_chains_exchange_async(self._h, r0 + i))
@@ -472,14 +504,18 @@ class Chains:
         return (pooled, ps) if per_series else pooled
 
     def run_sampled(self, steps_per_sample: int, n_samples: int,
-                    max_retries: int = DEFAULT_MAX_RETRIES, tally: bool = False) -> None:
+                    max_retries: int = DEFAULT_MAX_RETRIES, tally: bool = False,
+                    geometry: bool = False) -> None:
         """``n_samples`` x (``steps_per_sample`` steps, one recorded sample), enqueued back to
-        back and waited for once.  With ``tally`` every sample's plans are tallied as well."""
+        back and waited for once.  With ``tally`` every sample's plans are tallied as well, with
+        ``geometry`` their districts are measured (run, tally, geometry, record)."""
         L = _lib.load()
         for _ in range(int(n_samples)):
             check(L.fw_chains_run_async(self._h, int(steps_per_sample), int(max_retries)))
             if tally:
                 self.tally()
+            if geometry:
+                self.geometry()
             self.record()
         self.sync()
 
@@ -565,6 +601,54 @@ class Chains:
     def tally_reset(self) -> None:
         check(_lib.load().fw_chains_tally_reset(self._h))
         self._tally_base = 0
+
+    # ------------------------------------------------------------- district geometry
+    def set_geometry(self, edge_weights=None, area=None, exterior=None) -> None:
+        """What the per-district geometry sums (fw_chains_set_geometry): integer
+        ``edge_weights`` [n_edges] in ``Graph.edges()`` order (shared perimeters; None: every
+        edge 1), ``area`` [n] (None: every node 1) and ``exterior`` [n], a node's exterior
+        perimeter (None: 0).  Values >= 0, every total below 2^31 (``compactness.quantise``
+        and ``Graph.edge_column`` make such arrays).  May be repeated: it replaces the arrays
+        and zeroes the histogram and the count."""
+        arrays = check_geometry_arrays(self.dgraph.n, self.dgraph.n_edges, edge_weights, area,
+                                       exterior)
+        check(_lib.load().fw_chains_set_geometry(self._h, *(ptr(a) for a in arrays)))
+        self.geometry_arrays = arrays
+        self._geometry_base = 0
+
+    def geometry(self) -> None:
+        """Measure every chain's current districts on the handle's stream, behind the runs
+        already there (fw_chains_geometry_async); no wait."""
+        check(_lib.load().fw_chains_geometry_async(self._h))
+
+    def geometry_info(self) -> dict:
+        info = np.zeros(5, np.int64)
+        check(_lib.load().fw_chains_geometry_info(self._h, ptr(info)))
+        return {"edge_weights": bool(info[0]), "label_bits": int(info[1]),
+                "n_groups": int(info[2]), "n_edges": int(info[3]),
+                "n_measured": int(info[4]) + self._geometry_base}
+
+    def _read_geometry(self, what, arr):
+        check(_lib.load().fw_chains_read_geometry(self._h, what, ptr(arr), arr.nbytes))
+        return arr
+
+    def district_geometry(self) -> np.ndarray:
+        """int64 [n_chains, k, 5] of the last measurement: per district {nodes, cut edges,
+        interior perimeter, exterior perimeter, area}, the field indices ``compactness.NODES``
+        .. ``compactness.AREA``."""
+        return self._read_geometry(_lib.GEOM_DISTRICTS,
+                                   np.empty((self.n_chains, self.k, 5), np.int64))
+
+    def geometry_hist(self) -> np.ndarray:
+        """uint64 [n_groups, n_edges + 1]: measured districts per cut-edge count, over all
+        measurements; one group, or one per rung under a ladder."""
+        info = self.geometry_info()
+        return self._read_geometry(_lib.GEOM_HIST,
+                                   np.empty((info["n_groups"], info["n_edges"] + 1), np.uint64))
+
+    def geometry_reset(self) -> None:
+        check(_lib.load().fw_chains_geometry_reset(self._h))
+        self._geometry_base = 0
 
     # ------------------------------------------------------------- sampled waits
     def enable_sampled_waits(self) -> None:
@@ -654,6 +738,13 @@ class Chains:
                 ck["tally_names"] = np.array(self.column_names, dtype=np.str_)
             ck["tally_hist"] = self.seat_hist()
             ck["n_tallied"] = np.int64(self.tally_info()["n_tallied"])
+        if self.geometry_arrays is not None:
+            for key, a in zip(("geometry_edge_weights", "geometry_area", "geometry_exterior"),
+                              self.geometry_arrays):
+                if a is not None:
+                    ck[key] = a
+            ck["geometry_hist"] = self.geometry_hist()
+            ck["n_measured"] = np.int64(self.geometry_info()["n_measured"])
         return ck
 
     def restore(self, ck: dict) -> None:
@@ -746,6 +837,15 @@ class Chains:
                                           ptr(hist) if hist.size else None, hist.nbytes))
             self._tally_base = int(ck["n_tallied"]) - (self.tally_info()["n_tallied"] -
                                                        self._tally_base)
+        # the geometry after the ladder too: set_ladder re-sizes its histogram by rung
+        if "geometry_hist" in ck:
+            self.set_geometry(*(np.asarray(ck[key]) if key in ck else None for key in
+                                ("geometry_edge_weights", "geometry_area", "geometry_exterior")))
+            hist = np.ascontiguousarray(ck["geometry_hist"], np.uint64)
+            if hist.shape != self.geometry_hist().shape:
+                raise ValueError("checkpoint of another geometry histogram shape")
+            check(L.fw_chains_write_geometry(self._h, _lib.GEOM_HIST, ptr(hist), hist.nbytes))
+            self._geometry_base = int(ck["n_measured"])  # set_geometry zeroed the handle's count
 
     def save_checkpoint(self, path: str) -> None:
         ck = self.checkpoint()

@@ -204,6 +204,15 @@ struct fw_chains {
   int64_t* d_tal_sums = nullptr;
   int32_t* d_tal_seats = nullptr;            // [n_chains][FW_TALLY_MAX_EL][2] (n_el rows in use)
   unsigned long long* d_tal_hist = nullptr;  // room for 64 groups x 4 elections x (k + 1) bins
+  // fw_chains_set_geometry (geo_set false: none); FwGeomParams / FwGeomHistParams name the arrays
+  bool geo_set = false, geo_have = false;  // geo_have: measured since the last set_geometry
+  int64_t n_measured = 0;
+  FwGeomPlan geo_plan{};
+  uint32_t* d_geo_w = nullptr;     // [n_edges] or null (unit weights)
+  uint32_t* d_geo_area = nullptr;  // [n] or null (unit areas)
+  uint32_t* d_geo_ext = nullptr;   // [n] or null (no exterior perimeter)
+  int64_t* d_geo_out = nullptr;    // [n_chains][k][5]
+  unsigned long long* d_geo_hist = nullptr;  // [n_groups][n_edges + 1], the group count in force
 };
 
 namespace {
@@ -292,6 +301,11 @@ bool plan_valid(const fw_graph* g, const int16_t* lab, int k, int64_t lo, int64_
       return false;
     }
   return true;
+}
+
+// the per-district cut histogram of a handle with n_groups groups
+size_t geo_hist_bytes(const fw_chains* c, int n_groups) {
+  return sizeof(unsigned long long) * (size_t)n_groups * (size_t)(c->g->nnz / 2 + 1);
 }
 
 size_t ring_bins(int r) { return (size_t)r * (size_t)r + 1; }
@@ -516,7 +530,8 @@ void fw_chains_destroy(fw_chains* c) {
                   c->d_wsamp,  c->d_wlp,   c->d_lad_thr, c->d_lad_thr53, c->d_logb, c->d_rung,
                   c->d_chain_of, c->d_gmin, c->d_snap, c->d_rstats,
                   c->d_ser_cut, c->d_ser_bn, c->d_ser_rung,
-                  c->d_tal_cols, c->d_tal_sums, c->d_tal_seats, c->d_tal_hist};
+                  c->d_tal_cols, c->d_tal_sums, c->d_tal_seats, c->d_tal_hist,
+                  c->d_geo_w, c->d_geo_area, c->d_geo_ext, c->d_geo_out, c->d_geo_hist};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -1298,6 +1313,9 @@ int fw_chains_set_ladder(fw_chains* c, const double* thr_rows, const double* log
                          shared ? sizeof(double) * C * L : 0, shared ? sizeof(uint64_t) * C * L : 0};
   bool ok = true;
   for (int i = 0; i < 10 && ok; ++i) ok = sz[i] == 0 || hipMalloc(&nb[i], sz[i]) == hipSuccess;
+  // the per-district cut histogram is kept by rung: a new one for the new group count
+  unsigned long long* geo_hist = nullptr;
+  if (c->geo_set && ok) ok = hipMalloc(&geo_hist, geo_hist_bytes(c, n_rungs)) == hipSuccess;
   void* d_thr = shared ? nb[8] : (void*)c->d_thr;
   void* d_thr53 = shared ? nb[9] : (void*)c->d_thr53;
   const bool up =
@@ -1310,10 +1328,12 @@ int fw_chains_set_ladder(fw_chains* c, const double* thr_rows, const double* log
       hipMemset(nb[7], 0, sz[7]) == hipSuccess &&
       hipMemcpy(d_thr, thr.data(), sizeof(double) * C * L, hipMemcpyHostToDevice) == hipSuccess &&
       hipMemcpy(d_thr53, thr53.data(), sizeof(uint64_t) * C * L, hipMemcpyHostToDevice) ==
-          hipSuccess;
+          hipSuccess &&
+      (!geo_hist || hipMemset(geo_hist, 0, geo_hist_bytes(c, n_rungs)) == hipSuccess);
   if (!up) {
     for (void* b : nb)
       if (b) (void)hipFree(b);
+    if (geo_hist) (void)hipFree(geo_hist);
     return ok ? fail(FW_EHIP, "ladder upload failed")
               : fail(FW_ENOMEM, "ladder of %d rungs for %d chains", n_rungs, C);
   }
@@ -1330,6 +1350,10 @@ int fw_chains_set_ladder(fw_chains* c, const double* thr_rows, const double* log
   c->d_gmin = static_cast<int64_t*>(nb[5]);
   c->d_snap = static_cast<FwRungSnap*>(nb[6]);
   c->d_rstats = static_cast<fw_rung_stats*>(nb[7]);
+  if (geo_hist) {
+    (void)hipFree(c->d_geo_hist);
+    c->d_geo_hist = geo_hist;
+  }
   c->d_thr = static_cast<double*>(d_thr);
   c->d_thr53 = static_cast<uint64_t*>(d_thr53);
   c->p.thr = c->d_thr;
@@ -1873,6 +1897,184 @@ int fw_chains_tally_info(const fw_chains* c, int64_t info[5]) {
   info[2] = c->lb;
   info[3] = c->n_rungs ? c->n_rungs : 1;
   info[4] = c->n_tallied;
+  return FW_OK;
+}
+
+// ---------------------------------------------------------------- per-district geometry
+namespace {
+
+// a geometry array as the device keeps it: every value >= 0, the total below 2^31
+int geo_pack(const char* name, const int64_t* src, size_t len, std::vector<uint32_t>* out) {
+  out->clear();
+  if (!src) return FW_OK;
+  out->resize(len);
+  int64_t total = 0;
+  for (size_t i = 0; i < len; ++i) {
+    const int64_t v = src[i];
+    if (v < 0) return fail(FW_EINVAL, "%s: value %lld at index %zu is negative", name, (long long)v, i);
+    // v >= 2^31 alone is already too much; below it the running total cannot overflow
+    if (v >= (1ll << 31) || (total += v) >= (1ll << 31))
+      return fail(FW_EINVAL, "%s: the total must stay below 2^31", name);
+    (*out)[i] = (uint32_t)v;
+  }
+  return FW_OK;
+}
+
+int geo_bytes(const fw_chains* c, int32_t what, size_t* need) {
+  switch (what) {
+    case FW_GEOM_DISTRICTS:
+      *need = sizeof(int64_t) * (size_t)c->n_chains * c->k * 5;
+      return FW_OK;
+    case FW_GEOM_HIST:
+      *need = geo_hist_bytes(c, c->n_rungs ? c->n_rungs : 1);
+      return FW_OK;
+    default:
+      return fail(FW_EINVAL, "unknown geometry kind %d", what);
+  }
+}
+
+}  // namespace
+
+int fw_chains_set_geometry(fw_chains* c, const int64_t* edge_w, const int64_t* area,
+                           const int64_t* ext) {
+  if (!c) return fail(FW_EINVAL, "fw_chains_set_geometry: null");
+  const size_t n = (size_t)c->g->n, E = (size_t)(c->g->nnz / 2);
+  std::vector<uint32_t> hw, ha, he;
+  if (const int rc = geo_pack("edge weights", edge_w, E, &hw)) return rc;
+  if (const int rc = geo_pack("area", area, n, &ha)) return rc;
+  if (const int rc = geo_pack("exterior", ext, n, &he)) return rc;
+  HIPCHK(hipSetDevice(c->g->device));
+  HIPCHK(hipStreamSynchronize(c->stream));  // a measurement in flight reads the old arrays
+  // the new buffers first: on failure the handle keeps what it had
+  const int n_groups = c->n_rungs ? c->n_rungs : 1;
+  const std::vector<uint32_t>* host[3] = {&hw, &ha, &he};
+  uint32_t* dev[3] = {nullptr, nullptr, nullptr};
+  int64_t* d_out = c->d_geo_out;
+  unsigned long long* d_hist = c->d_geo_hist;
+  bool ok = true;
+  for (int i = 0; i < 3 && ok; ++i)
+    ok = host[i]->empty() || hipMalloc(&dev[i], sizeof(uint32_t) * host[i]->size()) == hipSuccess;
+  ok = ok &&
+       (d_out || hipMalloc(&d_out, sizeof(int64_t) * (size_t)c->n_chains * c->k * 5) == hipSuccess) &&
+       (d_hist || hipMalloc(&d_hist, geo_hist_bytes(c, n_groups)) == hipSuccess);
+  bool up = ok;
+  for (int i = 0; i < 3 && up; ++i)
+    up = host[i]->empty() || hipMemcpy(dev[i], host[i]->data(), sizeof(uint32_t) * host[i]->size(),
+                                       hipMemcpyHostToDevice) == hipSuccess;
+  up = up && hipMemset(d_hist, 0, geo_hist_bytes(c, n_groups)) == hipSuccess;
+  if (!up) {
+    for (uint32_t* d : dev)
+      if (d) (void)hipFree(d);
+    if (d_out && !c->d_geo_out) (void)hipFree(d_out);
+    if (d_hist && !c->d_geo_hist) (void)hipFree(d_hist);
+    (void)hipGetLastError();
+    return ok ? fail(FW_EHIP, "geometry upload failed")
+              : fail(FW_ENOMEM, "geometry of %d chains", c->n_chains);
+  }
+  uint32_t* old[] = {c->d_geo_w, c->d_geo_area, c->d_geo_ext};
+  for (uint32_t* b : old)
+    if (b) (void)hipFree(b);
+  c->d_geo_w = dev[0];
+  c->d_geo_area = dev[1];
+  c->d_geo_ext = dev[2];
+  c->d_geo_out = d_out;
+  c->d_geo_hist = d_hist;
+  fw_geometry_plan(c->g->n, c->k, c->lb, dev[0] != nullptr, &c->geo_plan);
+  c->geo_set = true;
+  c->geo_have = false;
+  c->n_measured = 0;
+  return FW_OK;
+}
+
+int fw_chains_geometry_async(fw_chains* c) {
+  if (!c) return fail(FW_EINVAL, "null handle");
+  if (!c->geo_set) return fail(FW_ESTATE, "fw_chains_geometry_async: no geometry is set");
+  HIPCHK(hipSetDevice(c->g->device));
+  FwGeomParams p{};
+  p.labels = c->d_labels;
+  p.lab_stride = c->p.lab_stride;
+  p.eu = c->g->d_eu;
+  p.ew = c->g->d_ew;
+  p.ewt = c->d_geo_w;
+  p.area = c->d_geo_area;
+  p.ext = c->d_geo_ext;
+  p.out = c->d_geo_out;
+  p.n_chains = c->n_chains;
+  p.n = c->g->n;
+  p.n_edges = c->g->nnz / 2;
+  p.k = c->k;
+  p.lb = c->lb;
+  p.lab_words = c->geo_plan.lab_words;
+  p.tile = c->geo_plan.tile;
+  p.bins = c->geo_plan.bins;
+  p.nw = c->geo_plan.nw;
+  // like the exchange, record and tally steps: the run timing events are left alone
+  int le = fw_launch_geometry(p, c->geo_plan.lds_bytes, c->stream);
+  if (le != 0)
+    return fail(FW_EHIP, "geometry launch failed: %s", hipGetErrorString((hipError_t)le));
+  FwGeomHistParams h{};
+  h.G = c->d_geo_out;
+  h.rung = c->n_rungs ? c->d_rung : nullptr;
+  h.hist = c->d_geo_hist;
+  h.n_chains = c->n_chains;
+  h.k = c->k;
+  h.n_groups = c->n_rungs ? c->n_rungs : 1;
+  h.n_edges = p.n_edges;
+  le = fw_launch_geometry_hist(h, c->stream);
+  if (le != 0)
+    return fail(FW_EHIP, "geometry histogram launch failed: %s", hipGetErrorString((hipError_t)le));
+  c->geo_have = true;
+  c->n_measured += 1;
+  return FW_OK;
+}
+
+int fw_chains_read_geometry(fw_chains* c, int32_t what, void* dst, size_t bytes) {
+  if (!c) return fail(FW_EINVAL, "fw_chains_read_geometry: null");
+  size_t need = 0;
+  if (const int rc = geo_bytes(c, what, &need)) return rc;
+  if (!c->geo_set) return fail(FW_ESTATE, "fw_chains_read_geometry: no geometry is set");
+  if (what == FW_GEOM_DISTRICTS && !c->geo_have)
+    return fail(FW_ESTATE, "fw_chains_read_geometry: nothing has been measured yet");
+  if (bytes < need || !dst) return fail(FW_EINVAL, "the geometry needs %zu bytes", need);
+  HIPCHK(hipSetDevice(c->g->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const void* src = what == FW_GEOM_DISTRICTS ? (const void*)c->d_geo_out : (const void*)c->d_geo_hist;
+  HIPCHK(hipMemcpy(dst, src, need, hipMemcpyDeviceToHost));
+  return FW_OK;
+}
+
+int fw_chains_write_geometry(fw_chains* c, int32_t what, const void* src, size_t bytes) {
+  if (!c) return fail(FW_EINVAL, "fw_chains_write_geometry: null");
+  if (what != FW_GEOM_HIST)
+    return fail(FW_EINVAL, "fw_chains_write_geometry: only FW_GEOM_HIST can be written (got %d)", what);
+  if (!c->geo_set) return fail(FW_ESTATE, "fw_chains_write_geometry: no geometry is set");
+  size_t need = 0;
+  if (const int rc = geo_bytes(c, what, &need)) return rc;
+  if (bytes < need || !src) return fail(FW_EINVAL, "the geometry histogram needs %zu bytes", need);
+  HIPCHK(hipSetDevice(c->g->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpy(c->d_geo_hist, src, need, hipMemcpyHostToDevice));
+  return FW_OK;
+}
+
+int fw_chains_geometry_reset(fw_chains* c) {
+  if (!c) return fail(FW_EINVAL, "null handle");
+  if (c->d_geo_hist) {
+    HIPCHK(hipSetDevice(c->g->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemset(c->d_geo_hist, 0, geo_hist_bytes(c, c->n_rungs ? c->n_rungs : 1)));
+  }
+  c->n_measured = 0;
+  return FW_OK;
+}
+
+int fw_chains_geometry_info(const fw_chains* c, int64_t info[5]) {
+  if (!c || !info) return fail(FW_EINVAL, "fw_chains_geometry_info: null");
+  info[0] = c->d_geo_w ? 1 : 0;
+  info[1] = c->lb;
+  info[2] = c->n_rungs ? c->n_rungs : 1;
+  info[3] = c->g->nnz / 2;
+  info[4] = c->n_measured;
   return FW_OK;
 }
 

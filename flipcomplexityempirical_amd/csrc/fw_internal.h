@@ -267,6 +267,44 @@ struct FwSeatsParams {
   int32_t n_chains, k, n_cols, n_el, n_groups;
 };
 
+// ---- per-district geometry (fw_chains_set_geometry, fw_geometry.hip) ---------------------
+#define FW_GEOM_TILE 1024   // edges / nodes staged in LDS at a time (a multiple of 64)
+#define FW_GEOM_MAX_NW 16   // waves (chains) per workgroup at the most
+
+// the launch plan (fw_geometry_plan): dwords of a wave's resident label copy, the tile, the
+// quantities binned per walk (0: register accumulators) and the waves per workgroup
+struct FwGeomPlan {
+  int32_t lab_words, tile, bins, nw, lds_bytes;
+};
+
+// fw_chains_geometry_async: out[c][d] = {nodes, cut edges, interior perimeter, exterior
+// perimeter, area} of district d of chain c
+struct FwGeomParams {
+  const uint8_t* labels;  // packed lb-bit label records, chain c at labels + c * lab_stride
+  int64_t lab_stride;     // bytes, a multiple of 16
+  const int32_t* eu;      // [n_edges] canonical edge endpoints (u < w)
+  const int32_t* ew;
+  const uint32_t* ewt;    // [n_edges] edge weights, or null (unit weights: nothing is read)
+  const uint32_t* area;   // [n] or null (1 each)
+  const uint32_t* ext;    // [n] or null (0 each)
+  int64_t* out;           // [n_chains][k][5]
+  int32_t n_chains, n, n_edges, k, lb;
+  int32_t lab_words, tile, bins, nw;  // FwGeomPlan
+};
+
+// hist[g][out[c][d][1]] += 1 for every district, g = rung[c] (0 without a ladder)
+struct FwGeomHistParams {
+  const int64_t* G;          // [n_chains][k][5]
+  const int32_t* rung;       // [n_chains] or null
+  unsigned long long* hist;  // [n_groups][n_edges + 1]
+  int32_t n_chains, k, n_groups, n_edges;
+};
+
+// Host-side launchers implemented in fw_geometry.hip.
+void fw_geometry_plan(int n, int k, int lb, bool has_w, FwGeomPlan* out);
+int fw_launch_geometry(const FwGeomParams& p, int lds_bytes, void* stream);
+int fw_launch_geometry_hist(const FwGeomHistParams& h, void* stream);
+
 // Host-side launchers implemented in fw_tally.hip.
 void fw_tally_plan(int k, int lb, int* nw, int* lds_bytes);
 int fw_launch_tally(const FwTallyParams& t, void* stream);

@@ -37,6 +37,7 @@ class Graph:
     nodes: List[Hashable] = field(default_factory=list)  # original node keys, by id
     grid_w: int = 0  # >0: this is the row-major grid_w-wide grid
     node_attrs: Optional[List[Dict[str, Any]]] = None
+    edge_attrs: Optional[List[Dict[str, Any]]] = None  # per edge, in ``edges()`` order
 
     # ------------------------------------------------------------------ basics
     @property
@@ -99,6 +100,25 @@ class Graph:
                                      f"integer: {v!r}") from None
         return out
 
+    def edge_column(self, name: str, scale=1) -> np.ndarray:
+        """int64 [n_edges]: edge attribute ``name`` times ``scale``, rounded, in ``edges()``
+        order (``Chains.set_geometry``'s edge weights, e.g. ``shared_perim``), through
+        ``compactness.quantise``.  ValueError for a missing or non-numeric attribute."""
+        from .compactness import quantise
+        if self.edge_attrs is None:
+            raise ValueError("the graph carries no edge attributes")
+        vals = np.empty(self.n_edges, np.float64)
+        for e, ((u, w), attrs) in enumerate(zip(self.edges(), self.edge_attrs)):
+            ends = (self.nodes[u], self.nodes[w]) if self.nodes else (int(u), int(w))
+            if name not in attrs:
+                raise ValueError(f"edge {ends!r} has no attribute {name!r}")
+            try:
+                vals[e] = float(attrs[name])
+            except (TypeError, ValueError):
+                raise ValueError(f"attribute {name!r} of edge {ends!r} is not a number: "
+                                 f"{attrs[name]!r}") from None
+        return quantise(vals, scale)
+
     def validate(self) -> None:
         rp, col = self.rowptr, self.col
         if rp[0] != 0 or rp[-1] != len(col) or np.any(np.diff(rp) < 0):
@@ -114,7 +134,9 @@ class Graph:
     # ------------------------------------------------------------ constructors
     @classmethod
     def from_adjacency(cls, nodes: Sequence[Hashable], adj: Dict[Hashable, Sequence[Hashable]],
-                       pop: Optional[Sequence[int]] = None, node_attrs=None) -> "Graph":
+                       pop: Optional[Sequence[int]] = None, node_attrs=None,
+                       edge_attrs=None) -> "Graph":
+        """``edge_attrs``: a dict {(a, b): attributes} over node keys, either orientation."""
         try:
             order = sorted(nodes)
         except TypeError:
@@ -135,6 +157,12 @@ class Graph:
             attrs = [amap[k] for k in order]
         g = cls(rowptr=rowptr, col=col, pop=p, nodes=list(order), node_attrs=attrs)
         g.validate()
+        if edge_attrs is not None:
+            g.edge_attrs = []
+            for u, w in g.edges():
+                a, b = order[u], order[w]
+                d = edge_attrs.get((a, b))
+                g.edge_attrs.append(dict(edge_attrs.get((b, a), {}) if d is None else d))
         g.grid_w = detect_grid(g)
         return g
 
@@ -145,7 +173,8 @@ class Graph:
         pop = None
         if pop_col is not None:
             pop = [int(G.nodes[k][pop_col]) for k in nodes]
-        return cls.from_adjacency(nodes, adj, pop, [dict(G.nodes[k]) for k in nodes])
+        eattrs = {(a, b): d for a, b, d in G.edges(data=True) if a != b}
+        return cls.from_adjacency(nodes, adj, pop, [dict(G.nodes[k]) for k in nodes], eattrs)
 
     @classmethod
     def from_json(cls, path: str, pop_col: Optional[str] = "TOTPOP") -> "Graph":
@@ -161,7 +190,9 @@ class Graph:
         pop = None
         if pop_col is not None:
             pop = [int(d[pop_col]) for d in data["nodes"]]
-        return cls.from_adjacency(nodes, adj, pop, data["nodes"])
+        eattrs = {(nid, e["id"]): {key: val for key, val in e.items() if key != "id"}
+                  for i, nid in enumerate(nodes) for e in data["adjacency"][i] if e["id"] != nid}
+        return cls.from_adjacency(nodes, adj, pop, data["nodes"], eattrs)
 
 
 def detect_grid(g: Graph) -> int:

@@ -165,12 +165,13 @@ const char* fw_last_error(void);
  * schedules; 0.4: ring observable, checkpoint/resume; 0.5: sampled geometric waits;
  * 0.6: fw_chains_launch_info; 0.7: fw_build_info; the ladder entry points
  * fw_chains_set_ladder / fw_chains_exchange_async, the observable-series entry points and
- * the tally entry points arrived in 0.7 without a bump). */
+ * the tally entry points and the geometry entry points arrived in 0.7 without a bump). */
 int32_t fw_version(void);
 
 /* Provenance of this build (static string, never NULL): "src=<sha256 of the flip
  * kernels, headers and ABI source> flags=<compiler flags, including any -D>
- * series=<sha256 of fw_series.hip> tally=<sha256 of fw_tally.hip>".  Bench lines and PMC
+ * series=<sha256 of fw_series.hip> tally=<sha256 of fw_tally.hip> geom=<sha256 of
+ * fw_geometry.hip>".  Bench lines and PMC
  * profiles carry it, so a measurement names the code it measured. */
 const char* fw_build_info(void);
 
@@ -460,6 +461,58 @@ int fw_chains_read_tally(fw_chains* c, int32_t what, void* dst, size_t bytes);
 int fw_chains_write_tally(fw_chains* c, int32_t what, const void* src, size_t bytes);
 int fw_chains_tally_reset(fw_chains* c);
 int fw_chains_tally_info(const fw_chains* c, int64_t info[5]);
+
+/* ---- per-district geometry: cut edges, perimeters, areas -------------------------------
+ * GerryChain's cut_edges_by_part, interior_boundaries, exterior_boundaries, perimeter, area and
+ * polsby_popper (the reference imports GeographicPartition; its census graphs carry
+ * shared_perim on the edges, boundary_perim and area on the nodes), measured for every chain's
+ * current plan on the device and between launches, as the exchange, record and tally steps are
+ * placed; no run kernel changes.  Every result is an exact integer; the scores are formed on
+ * the host (compactness.py).
+ *
+ * fw_chains_set_geometry: edge_w int64 [n_edges] indexed by the canonical edge id (pairs u < w
+ * in CSR row order) or NULL (every weight 1: no weight array is kept or read); area int64 [n]
+ * or NULL (every node has area 1); ext int64 [n], a node's exterior perimeter, or NULL (0).
+ * Every value >= 0 and the total of each array < 2^31 (so any district sum fits 32 bits, a
+ * district's interior perimeter being at most the total edge weight; the device keeps the
+ * values as 32-bit), else FW_EINVAL, checked on the host before the device is touched.  May be
+ * repeated: it replaces the arrays and zeroes the histogram and n_measured.
+ *
+ * fw_chains_geometry_async (FW_ESTATE before fw_chains_set_geometry) enqueues on the handle's
+ * stream, with no host synchronisation and without touching fw_chains_last_kernel_ms, for
+ * every chain c (stuck chains like any other) with lab its current plan:
+ *   G[c][d][0] = number of nodes labelled d
+ *   G[c][d][1] = number of edges (u, w) with lab[u] != lab[w] and d in {lab[u], lab[w]}
+ *   G[c][d][2] = sum of edge_w over those edges           (interior perimeter)
+ *   G[c][d][3] = sum of ext over the nodes labelled d     (exterior perimeter)
+ *   G[c][d][4] = sum of area over the nodes labelled d
+ *   hist[g][G[c][d][1]] += 1 for every district d, g = the chain's current rung under a
+ *                ladder, else 0.
+ * The host counter n_measured is incremented at enqueue.  Every G value is a plain vector
+ * store from one owner (no atomics, no dependence on thread order); the histogram is
+ * accumulated with integer atomics, whose sum does not depend on the order.
+ *
+ * fw_chains_read_geometry synchronises, then copies
+ *   FW_GEOM_DISTRICTS  int64  [n_chains][k][5]          of the last measurement
+ *   FW_GEOM_HIST       uint64 [n_groups][n_edges + 1]   accumulated over all measurements;
+ *                                                       n_groups = n_rungs, or 1 without a ladder
+ * FW_ESTATE before fw_chains_set_geometry, and for DISTRICTS when nothing was measured since
+ * it; FW_EINVAL for a buffer that is too small.  fw_chains_write_geometry restores FW_GEOM_HIST
+ * (checkpoints; n_measured is not changed); fw_chains_geometry_reset zeroes the histogram and
+ * n_measured.  fw_chains_geometry_info: info = {has edge weights (0 / 1), label bits per node
+ * of the handle's plans, n_groups, n_edges, n_measured}.  fw_chains_reset_observables leaves
+ * all of this alone; fw_chains_set_ladder on a handle with geometry set re-sizes the histogram
+ * for the new group count and zeroes it.  (These entry points arrived in 0.7 without a version
+ * bump.) */
+#define FW_GEOM_DISTRICTS 0
+#define FW_GEOM_HIST 1
+int fw_chains_set_geometry(fw_chains* c, const int64_t* edge_w /*[n_edges] or NULL*/,
+                           const int64_t* area /*[n] or NULL*/, const int64_t* ext /*[n] or NULL*/);
+int fw_chains_geometry_async(fw_chains* c);
+int fw_chains_read_geometry(fw_chains* c, int32_t what, void* dst, size_t bytes);
+int fw_chains_write_geometry(fw_chains* c, int32_t what, const void* src, size_t bytes);
+int fw_chains_geometry_reset(fw_chains* c);
+int fw_chains_geometry_info(const fw_chains* c, int64_t info[5]);
 
 /* Read a map (FW_MAP_*) of chains [chain0, chain0 + n_chains) as int64
  * [n_chains][len], or with FW_MAP_SUM its sum over those chains [len]; len is
