@@ -27,6 +27,7 @@
 #include <algorithm>
 
 #include "fw_device.h"
+#include "fw_window_rows.h"
 
 #ifdef FW_STAMPS
 // Diagnostic build only (libflipwalk_stamps.so): per-phase s_memtime shares.
@@ -320,39 +321,6 @@ __device__ __forceinline__ void weights4x(const LDS uint8_t* lab, int x0, int W,
 // bytes of w (each < 64) summed
 __device__ __forceinline__ uint32_t bsum4m(uint32_t v) { return (v * 0x01010101u) >> 24; }
 
-
-// window_verdict (fw_device.h, = the oracle's orc_window_verdict) with the four source
-// flood fills run side by side in row-lanes 0..3 instead of one after another.  Fills
-// of sources in one window component are equal and other fills disjoint, so the
-// sequential verdict is order-free: 1 if some fill holds every source, else 0 if some
-// fill touches no border, else -1 (undecided).  Row-uniform result.
-// Layout: window row r (0..6, v's row 3) in byte r, column c (0..6, v's column 3) at bit c;
-// bit 7 of every byte is a zero guard column, so a dilation needs no column masks (a shift
-// into the guard is removed by & A): 4 shifts, 2 ORs of three and one AND per 32-bit half.
-__device__ __forceinline__ int window_verdict8(uint64_t A, int q, int row, bool need, uint32_t& nflood) {
-#ifdef FW_STAMPS
-#define FLOOD_COUNT ++nflood
-#else
-#define FLOOD_COUNT
-#endif
-  constexpr uint64_t BORDER = 0x7Full | (0x7Full << 48) | 0x0001010101010101ull | 0x0040404040404040ull;
-  // sources up (row 2, column 3), left (3, 2), right (3, 4), down (4, 3)
-  const uint64_t src = A & ((1ull << 19) | (1ull << 26) | (1ull << 28) | (1ull << 35));
-  const int sb = q == 0 ? 19 : q == 1 ? 26 : q == 2 ? 28 : 35;
-  uint64_t x = (need && q < 4) ? src & (1ull << sb) : 0ull;
-  if (x) {
-    // two dilations per convergence test (same fixpoint, half the loop-exit tests)
-    for (;;) {
-      const uint64_t y = (x | (x << 1) | (x >> 1) | (x << 8) | (x >> 8)) & A;
-      x = (y | (y << 1) | (y >> 1) | (y << 8) | (y >> 8)) & A;
-      FLOOD_COUNT;
-      if (x == y) break;
-    }
-  }
-  const uint32_t full = rowbits(ballot(x != 0ull && (x & src) == src), row);
-  const uint32_t closed = rowbits(ballot(x != 0ull && (x & BORDER) == 0ull), row);
-  return full ? 1 : (closed ? 0 : -1);
-}
 
 // grid_race_bb (fw_device.h) run by every row at once on its own chain, in a 16-row x
 // 32-column window: row-lane q holds grid row vr - 8 + q, bit b column vc - 16 + b.  The
@@ -1277,37 +1245,45 @@ __device__ __forceinline__ void grid16_body(const FwRunParams& p) {
       // bitwise, not short-circuit: no exec-mask branches
       bool contig = (m == 1) | ((m >= 2) & (m - (lNE + lES + lSW + lWN) <= 1));
       bool need = go & pop_ok & (m >= 2) & !contig;
-      if (ballot(need)) {  // 7x7 window flood fill (window_verdict8's layout)
-        // read t: row-lane q takes window row 2t + q / 8, column q % 8 (column 7: the guard,
-        // never a cell), so row ballot t is bits 16t .. 16t + 15 of A
-        uint64_t A = 0;
-        bool inw[4];
-        uint32_t raw[4], lw[4];
-        int xw[4];
-        const int wcol = q & 7;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {  // branch-free: all four reads issued, then masked
-          const int wrow = 2 * t + (q >> 3);
-          const int rr = vr + wrow - 3, cw = vc + wcol - 3;
-          inw[t] = (wcol < 7) & (wrow < 7) & ((uint32_t)rr < (uint32_t)H) & ((uint32_t)cw < (uint32_t)W);
-          xw[t] = inw[t] ? mulW(rr, W) + cw : v;
-          raw[t] = lab[xw[t] >> 2];  // P::get's byte (2-bit labels) or nibble pair (4-bit)
-          if constexpr (LB != 2) raw[t] = P::get(lab, xw[t]);
+      if (ballot(need)) {  // 7x7 window flood fill, one window row per lane (fw_window_rows.h)
+        // row-lane q < 7 reads the dword pair that holds the seven labels of window row q
+        // (grid row vr - 3 + q, columns vc - 3 .. vc + 3; a row off the grid reads v's row
+        // instead).  The pair stays inside the slot or the word in front of it, as
+        // lab_window's does: columns < 0 (the word before the slot at x0 < 0), columns >= W
+        // (the next grid row, or the slot's padding and sums past row H - 1), rows off the
+        // grid, v itself and rows without need are masked to zero.
+        const int wr = vr - 3 + q;
+        const bool rin = (q < 7) & ((uint32_t)wr < (uint32_t)H);
+        const int wbit = (mulW(rin ? wr : vr, W) + vc - 3) * LB;  // >= -3 * LB
+        const int wi = wbit >> 5;                                // arithmetic: -1 at most
+        const LDS uint32_t* lw32 = reinterpret_cast<const LDS uint32_t*>(lab);
+        const uint32_t wlo = lw32[wi], whi = lw32[wi + 1];  // one ds_read2_b32
+        uint32_t cm = win_col_mask(vc, W);
+        cm = q == 3 ? cm & ~8u : cm;  // v (row 3, column 3)
+        cm = (rin & need) ? cm : 0u;
+        const uint32_t A4 = (win_row_mask<LB>(wlo, whi, (uint32_t)wbit & 31u, a) & cm) * 0x01010101u;
+        // the four sources' fills in the four bytes; a wave-uniform loop, two dilations per
+        // convergence test (same fixpoint, half the loop-exit tests)
+        uint32_t fx = win_seed(q, amb) & A4;
+        [[maybe_unused]] uint32_t nflood = 0;
+        for (;;) {
+          const uint32_t fy = win_dilate(fx, from_prev_row_lane(fx), from_next_row_lane(fx), A4);
+          fx = win_dilate(fy, from_prev_row_lane(fy), from_next_row_lane(fy), A4);
+          ++nflood;
+          if (!ballot(fx != fy)) break;
         }
-        // the four loads stay together (one LDS round trip): at the register limit the
-        // scheduler otherwise put each load's wait before the next load
-        if constexpr (!W2) __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) lw[t] = LB == 2 ? (raw[t] >> ((xw[t] & 3) << 1)) & 3u : raw[t];
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-          A |= (uint64_t)rowbits(ballot(inw[t] & (lw[t] == a)), row) << (ROW * t);
-        A &= ~(1ull << 27);  // v (row 3, column 3)
-        uint32_t nflood = 0;
-        const int wvd = window_verdict8(A, q, row, need, nflood);
+        // the lanes' verdict terms ORed over row-lanes 0..6 (a 3-step row_shr scan leaves
+        // them on lane 6): bits 7, 15, 23, 31 the fills' border flags, bit 0 a miss
+        const uint32_t ex4 = win_exist4(amb);
+        uint32_t vt = win_touch(fx, q) | (win_miss(fx, ex4) ? 1u : 0u);
+        vt |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)vt, 0x111, 0xF, 0xF, true);
+        vt |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)vt, 0x112, 0xF, 0xF, true);
+        vt |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)vt, 0x114, 0xF, 0xF, true);
+        vt = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)vt, 0x156, 0xF, 0xF, false);  // row_newbcast:6
+        const int wvd = win_verdict((vt & 1u) != 0u, vt, ex4);
         STAMP_COUNT(12, 1);
-        STAMP_COUNT(13, __builtin_amdgcn_readfirstlane(__reduce_max_sync(~0ull, nflood)));
-        if (wvd >= 0) {
+        STAMP_COUNT(13, nflood);
+        if (need & (wvd >= 0)) {
           contig = wvd == 1;
           need = false;
         }

@@ -171,7 +171,7 @@ int32_t fw_version(void);
 /* Provenance of this build (static string, never NULL): "src=<sha256 of the flip
  * kernels, headers and ABI source> flags=<compiler flags, including any -D>
  * series=<sha256 of fw_series.hip> tally=<sha256 of fw_tally.hip> geom=<sha256 of
- * fw_geometry.hip>".  Bench lines and PMC
+ * fw_geometry.hip> win=<sha256 of fw_window_rows.h>".  Bench lines and PMC
  * profiles carry it, so a measurement names the code it measured. */
 const char* fw_build_info(void);
 
