@@ -28,6 +28,8 @@ SERIES_MAX_LAG = 1023
 TALLY_SUMS, TALLY_SEATS, TALLY_HIST = 0, 1, 2
 TALLY_MAX_COLS, TALLY_MAX_ELECTIONS = 8, 4
 GEOM_DISTRICTS, GEOM_HIST = 0, 1
+OVERLAP_REFERENCE, OVERLAP_PARTNER = 0, 1
+OVERLAP_MATRIX, OVERLAP_DIST, OVERLAP_HIST, OVERLAP_REF = 0, 1, 2, 3
 
 STATS_DTYPE = np.dtype(
     [
@@ -117,6 +119,13 @@ SIGNATURES = [
     ("fw_chains_write_geometry", ctypes.c_int, [_P, _I32, _P, ctypes.c_size_t]),
     ("fw_chains_geometry_reset", ctypes.c_int, [_P]),
     ("fw_chains_geometry_info", ctypes.c_int, [_P, _P]),
+    ("fw_chains_set_reference", ctypes.c_int, [_P, _P, _I32]),
+    ("fw_chains_set_partners", ctypes.c_int, [_P, _P]),
+    ("fw_chains_overlap_async", ctypes.c_int, [_P, _I32]),
+    ("fw_chains_read_overlap", ctypes.c_int, [_P, _I32, _P, ctypes.c_size_t]),
+    ("fw_chains_write_overlap", ctypes.c_int, [_P, _I32, _P, ctypes.c_size_t]),
+    ("fw_chains_overlap_reset", ctypes.c_int, [_P]),
+    ("fw_chains_overlap_info", ctypes.c_int, [_P, _P]),
     ("fw_chains_read_map", ctypes.c_int, [_P, _I32, _I32, _I32, _I32, _P, ctypes.c_size_t]),
     ("fw_eval_flips", ctypes.c_int,
      [_P, _P, _I32, _P, _P, _I32, _I64, _I64, _P, _P, _P, _P]),

@@ -90,6 +90,8 @@ MAX_RUNGS = 64  # one wave per replica set, one lane per rung (fw_chains_exchang
 
 SERIES_KINDS = {"cut": _lib.SERIES_CUT, "bnodes": _lib.SERIES_BNODES, "rung": _lib.SERIES_RUNG}
 
+OVERLAP_KINDS = {"reference": _lib.OVERLAP_REFERENCE, "partner": _lib.OVERLAP_PARTNER}
+
 
 def ladder_layout(n_chains: int, n_rungs: int):
     """The default placement of ``Chains.set_ladder``: consecutive chains form a replica
@@ -269,6 +271,10 @@ class Chains:
         # no exterior); _geometry_base as _tally_base
         self.geometry_arrays = None
         self._geometry_base = 0
+        # set_partners: the array a checkpoint carries (the reference is read back from the
+        # handle); _overlap_base as _tally_base
+        self.partners = None
+        self._overlap_base = 0
         h = _lib.ctypes.c_void_p()
         check(L.fw_chains_create(dgraph.handle, self.n_chains, self.k, ptr(lab), per_chain,
                                  self.mode, self.pop_lo, self.pop_hi, ptr(self.thr), thr_per,
@@ -400,14 +406,16 @@ class Chains:
 
     def run_tempered(self, steps_per_round: int, n_rounds: int, round0: Optional[int] = None,
                      max_retries: int = DEFAULT_MAX_RETRIES, record: bool = False,
-                     tally: bool = False, geometry: bool = False) -> None:
+                     tally: bool = False, geometry: bool = False,
+                     overlap: bool | str = False) -> None:
         """``n_rounds`` x (``steps_per_round`` steps, one exchange), enqueued back to back and
         waited for once.  Rounds are numbered from ``round0`` (default: where the last call
         stopped, ``ladder_round``), which fixes the parity and the draws of each exchange.
         With ``record`` every round is run, record, exchange: a series sample carries the rung
         its chain has just run on; with ``tally`` every round is run, tally, exchange, so a
         plan is counted under that rung too, and with ``geometry`` its districts are measured
-        under it (run, tally, geometry, record, exchange)."""
+        under it, and with ``overlap`` (True: against the reference, or "partner") its distance
+        is binned under it (run, tally, geometry, overlap, record, exchange)."""
         if self.ladder_bases is None:
             raise ValueError("run_tempered needs a ladder (set_ladder)")
         r0 = self.ladder_round if round0 is None else int(round0)
@@ -418,6 +426,8 @@ class Chains:
                 self.tally()
             if geometry:
                 self.geometry()
+            if overlap:
+                self.overlap("reference" if overlap is True else overlap)
             if record:
                 self.record()
             check(L.fw_chains_exchange_async(self._h, r0 + i))
@@ -505,10 +515,11 @@ class Chains:
 
     def run_sampled(self, steps_per_sample: int, n_samples: int,
                     max_retries: int = DEFAULT_MAX_RETRIES, tally: bool = False,
-                    geometry: bool = False) -> None:
+                    geometry: bool = False, overlap: bool | str = False) -> None:
         """``n_samples`` x (``steps_per_sample`` steps, one recorded sample), enqueued back to
         back and waited for once.  With ``tally`` every sample's plans are tallied as well, with
-        ``geometry`` their districts are measured (run, tally, geometry, record)."""
+        ``geometry`` their districts are measured, with ``overlap`` (True: against the
+        reference, or "partner") they are compared (run, tally, geometry, overlap, record)."""
         L = _lib.load()
         for _ in range(int(n_samples)):
             check(L.fw_chains_run_async(self._h, int(steps_per_sample), int(max_retries)))
@@ -516,6 +527,8 @@ class Chains:
                 self.tally()
             if geometry:
                 self.geometry()
+            if overlap:
+                self.overlap("reference" if overlap is True else overlap)
             self.record()
         self.sync()
 
@@ -650,6 +663,93 @@ class Chains:
         check(_lib.load().fw_chains_geometry_reset(self._h))
         self._geometry_base = 0
 
+    # ------------------------------------------------------------- plan overlap and distance
+    def set_reference(self, plans=None) -> None:
+        """The plans ``overlap()`` compares with (fw_chains_set_reference).  ``None`` takes a
+        snapshot of every chain's current plan on the handle's stream, behind the runs already
+        there and with no wait; a 1-D plan [n] is shared by every chain; a 2-D array
+        [n_chains, n] gives each chain its own.  Labels lie in [0, k); a reference need not be
+        contiguous or balanced.  Replaces the reference and zeroes the distance histogram and
+        the count."""
+        if plans is None:
+            check(_lib.load().fw_chains_set_reference(self._h, None, 0))
+        else:
+            a = np.asarray(plans)
+            if a.dtype.kind not in "iu":
+                raise ValueError(f"reference plans must be integers, got {a.dtype}")
+            n = self.dgraph.n
+            if a.shape != (n,) and a.shape != (self.n_chains, n):
+                raise ValueError(f"reference plans must be [{n}] or [{self.n_chains}, {n}], "
+                                 f"got {a.shape}")
+            if a.size and (int(a.min()) < 0 or int(a.max()) >= self.k):
+                raise ValueError(f"reference labels must lie in [0, {self.k})")
+            a = np.ascontiguousarray(a, np.int16)
+            check(_lib.load().fw_chains_set_reference(self._h, ptr(a), 1 if a.ndim == 2 else 0))
+        self._overlap_base = 0
+
+    def set_partners(self, partner=None) -> None:
+        """The chain each chain is compared with by ``overlap("partner")``
+        (fw_chains_set_partners): int [n_chains], default ``(c + 1) % n_chains``.  Two
+        independent chains' overlap is the level a chain's overlap with its own past must
+        reach at stationarity."""
+        if partner is None:
+            if self.n_chains < 2:
+                raise ValueError("partners need at least two chains")
+            partner = (np.arange(self.n_chains) + 1) % self.n_chains
+        p = np.asarray(partner)
+        if p.dtype.kind not in "iu" or p.shape != (self.n_chains,):
+            raise ValueError(f"partner must be integers [{self.n_chains}]")
+        if p.size and (int(p.min()) < 0 or int(p.max()) >= self.n_chains):
+            raise ValueError(f"partners must lie in [0, {self.n_chains})")
+        p = np.ascontiguousarray(p, np.int32)
+        check(_lib.load().fw_chains_set_partners(self._h, ptr(p)))
+        self.partners = p
+
+    def overlap(self, against: str | int = "reference") -> None:
+        """Compare every chain's current plan with its reference ("reference") or with its
+        partner's current plan ("partner") on the handle's stream, behind the runs already
+        there (fw_chains_overlap_async); no wait."""
+        kind = OVERLAP_KINDS[against] if isinstance(against, str) else int(against)
+        check(_lib.load().fw_chains_overlap_async(self._h, kind))
+
+    def overlap_info(self) -> dict:
+        info = np.zeros(5, np.int64)
+        check(_lib.load().fw_chains_overlap_info(self._h, ptr(info)))
+        return {"reference": ("none", "shared", "per_chain")[int(info[0])],
+                "label_bits": int(info[1]), "n_groups": int(info[2]),
+                "partners": bool(info[3]), "n_measured": int(info[4]) + self._overlap_base}
+
+    def _read_overlap(self, what, arr):
+        check(_lib.load().fw_chains_read_overlap(self._h, what, ptr(arr), arr.nbytes))
+        return arr
+
+    def overlap_matrix(self) -> np.ndarray:
+        """int64 [n_chains, k, k] of the last measurement: O[c, d, e] = nodes the reference
+        labels d and the current plan labels e (``plandist`` turns it into scores)."""
+        return self._read_overlap(_lib.OVERLAP_MATRIX,
+                                  np.empty((self.n_chains, self.k, self.k), np.int64))
+
+    def plan_distance(self) -> np.ndarray:
+        """int32 [n_chains]: nodes labelled differently, last measurement."""
+        return self._read_overlap(_lib.OVERLAP_DIST, np.empty(self.n_chains, np.int32))
+
+    def distance_hist(self) -> np.ndarray:
+        """uint64 [n_groups, n + 1]: measured plans per distance, over all measurements; one
+        group, or one per rung under a ladder."""
+        return self._read_overlap(_lib.OVERLAP_HIST, np.empty(
+            (self.overlap_info()["n_groups"], self.dgraph.n + 1), np.uint64))
+
+    def reference(self) -> np.ndarray:
+        """int16 [n] (shared) or [n_chains, n]: the stored reference."""
+        kind = self.overlap_info()["reference"]
+        rows = self.n_chains if kind == "per_chain" else 1
+        out = self._read_overlap(_lib.OVERLAP_REF, np.empty((rows, self.dgraph.n), np.int16))
+        return out[0] if kind == "shared" else out
+
+    def overlap_reset(self) -> None:
+        check(_lib.load().fw_chains_overlap_reset(self._h))
+        self._overlap_base = 0
+
     # ------------------------------------------------------------- sampled waits
     def enable_sampled_waits(self) -> None:
         """Draw geom_wait per state object (grid_chain_sec11.py:147-148, cached and re-used
@@ -745,6 +845,14 @@ class Chains:
                     ck[key] = a
             ck["geometry_hist"] = self.geometry_hist()
             ck["n_measured"] = np.int64(self.geometry_info()["n_measured"])
+        ovl = self.overlap_info()
+        if ovl["reference"] != "none" or ovl["partners"]:
+            if ovl["reference"] != "none":
+                ck["overlap_reference"] = self.reference()
+            if ovl["partners"]:
+                ck["overlap_partners"] = self.partners
+            ck["distance_hist"] = self.distance_hist()
+            ck["n_overlaps"] = np.int64(ovl["n_measured"])
         return ck
 
     def restore(self, ck: dict) -> None:
@@ -846,6 +954,19 @@ class Chains:
                 raise ValueError("checkpoint of another geometry histogram shape")
             check(L.fw_chains_write_geometry(self._h, _lib.GEOM_HIST, ptr(hist), hist.nbytes))
             self._geometry_base = int(ck["n_measured"])  # set_geometry zeroed the handle's count
+        # and the overlap: its histogram is kept by rung as well
+        if "distance_hist" in ck:
+            if "overlap_reference" in ck:
+                self.set_reference(np.asarray(ck["overlap_reference"]))
+            if "overlap_partners" in ck:
+                self.set_partners(np.asarray(ck["overlap_partners"]))
+            hist = np.ascontiguousarray(ck["distance_hist"], np.uint64)
+            if hist.shape != self.distance_hist().shape:
+                raise ValueError("checkpoint of another distance histogram shape")
+            check(L.fw_chains_write_overlap(self._h, _lib.OVERLAP_HIST, ptr(hist), hist.nbytes))
+            # the handle's own count went on unless a reference was set just now
+            self._overlap_base = int(ck["n_overlaps"]) - (self.overlap_info()["n_measured"] -
+                                                          self._overlap_base)
 
     def save_checkpoint(self, path: str) -> None:
         ck = self.checkpoint()

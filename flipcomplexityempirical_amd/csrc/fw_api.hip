@@ -213,6 +213,16 @@ struct fw_chains {
   uint32_t* d_geo_ext = nullptr;   // [n] or null (no exterior perimeter)
   int64_t* d_geo_out = nullptr;    // [n_chains][k][5]
   unsigned long long* d_geo_hist = nullptr;  // [n_groups][n_edges + 1], the group count in force
+  // fw_chains_set_reference / fw_chains_set_partners; FwOverlapParams names the arrays
+  int32_t ovl_ref = 0;        // 0: no reference, 1: one shared row, 2: a row per chain
+  bool ovl_partners = false;
+  int32_t ovl_last = -1;      // what MATRIX and DIST hold: FW_OVERLAP_REFERENCE / _PARTNER, -1: nothing
+  int64_t ovl_measured = 0;
+  uint32_t* d_ovl_ref = nullptr;      // [n_chains][ovl_words4]
+  int32_t* d_ovl_partner = nullptr;   // [n_chains]
+  int64_t* d_ovl_O = nullptr;         // [n_chains][k][k]
+  int32_t* d_ovl_dist = nullptr;      // [n_chains]
+  unsigned long long* d_ovl_hist = nullptr;  // [n_groups][n + 1], the group count in force
 };
 
 namespace {
@@ -306,6 +316,11 @@ bool plan_valid(const fw_graph* g, const int16_t* lab, int k, int64_t lo, int64_
 // the per-district cut histogram of a handle with n_groups groups
 size_t geo_hist_bytes(const fw_chains* c, int n_groups) {
   return sizeof(unsigned long long) * (size_t)n_groups * (size_t)(c->g->nnz / 2 + 1);
+}
+
+// the plan-distance histogram of a handle with n_groups groups
+size_t ovl_hist_bytes(const fw_chains* c, int n_groups) {
+  return sizeof(unsigned long long) * (size_t)n_groups * (size_t)(c->g->n + 1);
 }
 
 size_t ring_bins(int r) { return (size_t)r * (size_t)r + 1; }
@@ -531,7 +546,8 @@ void fw_chains_destroy(fw_chains* c) {
                   c->d_chain_of, c->d_gmin, c->d_snap, c->d_rstats,
                   c->d_ser_cut, c->d_ser_bn, c->d_ser_rung,
                   c->d_tal_cols, c->d_tal_sums, c->d_tal_seats, c->d_tal_hist,
-                  c->d_geo_w, c->d_geo_area, c->d_geo_ext, c->d_geo_out, c->d_geo_hist};
+                  c->d_geo_w, c->d_geo_area, c->d_geo_ext, c->d_geo_out, c->d_geo_hist,
+                  c->d_ovl_ref, c->d_ovl_partner, c->d_ovl_O, c->d_ovl_dist, c->d_ovl_hist};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -1316,6 +1332,9 @@ int fw_chains_set_ladder(fw_chains* c, const double* thr_rows, const double* log
   // the per-district cut histogram is kept by rung: a new one for the new group count
   unsigned long long* geo_hist = nullptr;
   if (c->geo_set && ok) ok = hipMalloc(&geo_hist, geo_hist_bytes(c, n_rungs)) == hipSuccess;
+  // so is the plan-distance histogram
+  unsigned long long* ovl_hist = nullptr;
+  if (c->d_ovl_hist && ok) ok = hipMalloc(&ovl_hist, ovl_hist_bytes(c, n_rungs)) == hipSuccess;
   void* d_thr = shared ? nb[8] : (void*)c->d_thr;
   void* d_thr53 = shared ? nb[9] : (void*)c->d_thr53;
   const bool up =
@@ -1329,11 +1348,13 @@ int fw_chains_set_ladder(fw_chains* c, const double* thr_rows, const double* log
       hipMemcpy(d_thr, thr.data(), sizeof(double) * C * L, hipMemcpyHostToDevice) == hipSuccess &&
       hipMemcpy(d_thr53, thr53.data(), sizeof(uint64_t) * C * L, hipMemcpyHostToDevice) ==
           hipSuccess &&
-      (!geo_hist || hipMemset(geo_hist, 0, geo_hist_bytes(c, n_rungs)) == hipSuccess);
+      (!geo_hist || hipMemset(geo_hist, 0, geo_hist_bytes(c, n_rungs)) == hipSuccess) &&
+      (!ovl_hist || hipMemset(ovl_hist, 0, ovl_hist_bytes(c, n_rungs)) == hipSuccess);
   if (!up) {
     for (void* b : nb)
       if (b) (void)hipFree(b);
     if (geo_hist) (void)hipFree(geo_hist);
+    if (ovl_hist) (void)hipFree(ovl_hist);
     return ok ? fail(FW_EHIP, "ladder upload failed")
               : fail(FW_ENOMEM, "ladder of %d rungs for %d chains", n_rungs, C);
   }
@@ -1353,6 +1374,10 @@ int fw_chains_set_ladder(fw_chains* c, const double* thr_rows, const double* log
   if (geo_hist) {
     (void)hipFree(c->d_geo_hist);
     c->d_geo_hist = geo_hist;
+  }
+  if (ovl_hist) {
+    (void)hipFree(c->d_ovl_hist);
+    c->d_ovl_hist = ovl_hist;
   }
   c->d_thr = static_cast<double*>(d_thr);
   c->d_thr53 = static_cast<uint64_t*>(d_thr53);
@@ -2075,6 +2100,227 @@ int fw_chains_geometry_info(const fw_chains* c, int64_t info[5]) {
   info[2] = c->n_rungs ? c->n_rungs : 1;
   info[3] = c->g->nnz / 2;
   info[4] = c->n_measured;
+  return FW_OK;
+}
+
+// ---------------------------------------------------------------- plan overlap and distance
+namespace {
+
+// dwords of a record that hold labels, and a reference row's length (16-byte rows)
+int ovl_words(const fw_chains* c) { return (int)(((int64_t)c->g->n * c->lb + 31) / 32); }
+int ovl_row_words(const fw_chains* c) { return (ovl_words(c) + 3) & ~3; }
+
+// the buffers every overlap entry point shares, allocated by the first set_reference or
+// set_partners; on failure the handle keeps what it had
+int ovl_ensure(fw_chains* c) {
+  if (c->d_ovl_hist) return FW_OK;
+  const size_t C = (size_t)c->n_chains, kk = (size_t)c->k * c->k;
+  const size_t hist = ovl_hist_bytes(c, c->n_rungs ? c->n_rungs : 1);
+  void* nb[4] = {};
+  const size_t sz[4] = {sizeof(uint32_t) * C * ovl_row_words(c), sizeof(int64_t) * C * kk,
+                        sizeof(int32_t) * C, hist};
+  bool ok = true;
+  for (int i = 0; i < 4 && ok; ++i) ok = hipMalloc(&nb[i], sz[i]) == hipSuccess;
+  const bool up = ok && hipMemset(nb[3], 0, hist) == hipSuccess;
+  if (!up) {
+    for (void* b : nb)
+      if (b) (void)hipFree(b);
+    (void)hipGetLastError();
+    return ok ? fail(FW_EHIP, "overlap buffers could not be zeroed")
+              : fail(FW_ENOMEM, "overlap buffers of %d chains", c->n_chains);
+  }
+  c->d_ovl_ref = static_cast<uint32_t*>(nb[0]);
+  c->d_ovl_O = static_cast<int64_t*>(nb[1]);
+  c->d_ovl_dist = static_cast<int32_t*>(nb[2]);
+  c->d_ovl_hist = static_cast<unsigned long long*>(nb[3]);
+  return FW_OK;
+}
+
+int ovl_bytes(const fw_chains* c, int32_t what, size_t* need) {
+  switch (what) {
+    case FW_OVERLAP_MATRIX:
+      *need = sizeof(int64_t) * (size_t)c->n_chains * c->k * c->k;
+      return FW_OK;
+    case FW_OVERLAP_DIST:
+      *need = sizeof(int32_t) * (size_t)c->n_chains;
+      return FW_OK;
+    case FW_OVERLAP_HIST:
+      *need = ovl_hist_bytes(c, c->n_rungs ? c->n_rungs : 1);
+      return FW_OK;
+    case FW_OVERLAP_REF:
+      *need = sizeof(int16_t) * (size_t)(c->ovl_ref == 2 ? c->n_chains : 1) * c->g->n;
+      return FW_OK;
+    default:
+      return fail(FW_EINVAL, "unknown overlap kind %d", what);
+  }
+}
+
+}  // namespace
+
+int fw_chains_set_reference(fw_chains* c, const int16_t* labels, int32_t per_chain) {
+  if (!c) return fail(FW_EINVAL, "fw_chains_set_reference: null");
+  const int n = c->g->n, rows = labels && !per_chain ? 1 : c->n_chains;
+  const int row_words = ovl_row_words(c);
+  std::vector<uint8_t> packed;
+  if (labels) {
+    if (per_chain != 0 && per_chain != 1)
+      return fail(FW_EINVAL, "per_chain = %d is neither 0 nor 1", per_chain);
+    for (size_t i = 0; i < (size_t)rows * n; ++i)
+      if (labels[i] < 0 || labels[i] >= c->k)
+        return fail(FW_EINVAL, "reference label %d of node %zu (row %zu) outside [0, %d)",
+                    (int)labels[i], i % n, i / n, c->k);
+    packed.resize((size_t)rows * row_words * 4);
+    for (int i = 0; i < rows; ++i)
+      pack_labels(labels + (size_t)i * n, n, c->lb, packed.data() + (size_t)i * row_words * 4,
+                  row_words * 4);
+  }
+  HIPCHK(hipSetDevice(c->g->device));
+  if (const int rc = ovl_ensure(c)) return rc;
+  const size_t hist = ovl_hist_bytes(c, c->n_rungs ? c->n_rungs : 1);
+  if (labels) {
+    HIPCHK(hipStreamSynchronize(c->stream));  // a measurement in flight reads the old reference
+    HIPCHK(hipMemcpy(c->d_ovl_ref, packed.data(), packed.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(c->d_ovl_hist, 0, hist));
+  } else {
+    // a snapshot at this point of the stream: the label words of every record, not the group
+    // sums behind them; no host synchronisation
+    HIPCHK(hipMemcpy2DAsync(c->d_ovl_ref, (size_t)row_words * 4, c->d_labels,
+                            (size_t)c->p.lab_stride, (size_t)ovl_words(c) * 4,
+                            (size_t)c->n_chains, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(c->d_ovl_hist, 0, hist, c->stream));
+  }
+  c->ovl_ref = labels && !per_chain ? 1 : 2;
+  c->ovl_last = -1;
+  c->ovl_measured = 0;
+  return FW_OK;
+}
+
+int fw_chains_set_partners(fw_chains* c, const int32_t* partner) {
+  if (!c || !partner) return fail(FW_EINVAL, "fw_chains_set_partners: null");
+  for (int i = 0; i < c->n_chains; ++i)
+    if (partner[i] < 0 || partner[i] >= c->n_chains)
+      return fail(FW_EINVAL, "partner %d of chain %d outside [0, %d)", partner[i], i, c->n_chains);
+  HIPCHK(hipSetDevice(c->g->device));
+  if (const int rc = ovl_ensure(c)) return rc;
+  if (!c->d_ovl_partner)
+    if (hipMalloc(&c->d_ovl_partner, sizeof(int32_t) * (size_t)c->n_chains) != hipSuccess) {
+      (void)hipGetLastError();
+      c->d_ovl_partner = nullptr;
+      return fail(FW_ENOMEM, "partners of %d chains", c->n_chains);
+    }
+  HIPCHK(hipStreamSynchronize(c->stream));  // a measurement in flight reads the old partners
+  HIPCHK(hipMemcpy(c->d_ovl_partner, partner, sizeof(int32_t) * (size_t)c->n_chains,
+                   hipMemcpyHostToDevice));
+  c->ovl_partners = true;
+  if (c->ovl_last == FW_OVERLAP_PARTNER) c->ovl_last = -1;
+  return FW_OK;
+}
+
+int fw_chains_overlap_async(fw_chains* c, int32_t against) {
+  if (!c) return fail(FW_EINVAL, "null handle");
+  if (against != FW_OVERLAP_REFERENCE && against != FW_OVERLAP_PARTNER)
+    return fail(FW_EINVAL, "fw_chains_overlap_async: unknown kind %d", against);
+  if (against == FW_OVERLAP_REFERENCE && !c->ovl_ref)
+    return fail(FW_ESTATE, "fw_chains_overlap_async: no reference is set");
+  if (against == FW_OVERLAP_PARTNER && !c->ovl_partners)
+    return fail(FW_ESTATE, "fw_chains_overlap_async: no partners are set");
+  HIPCHK(hipSetDevice(c->g->device));
+  FwOverlapParams p{};
+  p.labels = c->d_labels;
+  p.lab_stride = c->p.lab_stride;
+  p.ref = c->d_ovl_ref;
+  p.ref_stride = c->ovl_ref == 2 ? ovl_row_words(c) : 0;
+  p.partner = against == FW_OVERLAP_PARTNER ? c->d_ovl_partner : nullptr;
+  p.O = c->d_ovl_O;
+  p.dist = c->d_ovl_dist;
+  p.n_chains = c->n_chains;
+  p.n = c->g->n;
+  p.k = c->k;
+  p.lb = c->lb;
+  p.lab_words = ovl_words(c);
+  int nw = 1, lds_bytes = 0;
+  fw_overlap_plan(c->k, &nw, &lds_bytes);
+  // like the exchange, record, tally and geometry steps: the run timing events are left alone
+  int le = fw_launch_overlap(p, nw, lds_bytes, c->stream);
+  if (le != 0)
+    return fail(FW_EHIP, "overlap launch failed: %s", hipGetErrorString((hipError_t)le));
+  FwOverlapHistParams h{};
+  h.dist = c->d_ovl_dist;
+  h.rung = c->n_rungs ? c->d_rung : nullptr;
+  h.hist = c->d_ovl_hist;
+  h.n_chains = c->n_chains;
+  h.n_groups = c->n_rungs ? c->n_rungs : 1;
+  h.n = p.n;
+  le = fw_launch_overlap_hist(h, c->stream);
+  if (le != 0)
+    return fail(FW_EHIP, "overlap histogram launch failed: %s", hipGetErrorString((hipError_t)le));
+  c->ovl_last = against;
+  c->ovl_measured += 1;
+  return FW_OK;
+}
+
+int fw_chains_read_overlap(fw_chains* c, int32_t what, void* dst, size_t bytes) {
+  if (!c) return fail(FW_EINVAL, "fw_chains_read_overlap: null");
+  size_t need = 0;
+  if (const int rc = ovl_bytes(c, what, &need)) return rc;
+  if (!c->d_ovl_hist)
+    return fail(FW_ESTATE, "fw_chains_read_overlap: neither a reference nor partners are set");
+  if ((what == FW_OVERLAP_MATRIX || what == FW_OVERLAP_DIST) && c->ovl_last < 0)
+    return fail(FW_ESTATE, "fw_chains_read_overlap: nothing has been measured yet");
+  if (what == FW_OVERLAP_REF && !c->ovl_ref)
+    return fail(FW_ESTATE, "fw_chains_read_overlap: no reference is set");
+  if (bytes < need || !dst) return fail(FW_EINVAL, "the overlap needs %zu bytes", need);
+  HIPCHK(hipSetDevice(c->g->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (what == FW_OVERLAP_REF) {
+    const int rows = c->ovl_ref == 2 ? c->n_chains : 1, row_bytes = ovl_row_words(c) * 4;
+    std::vector<uint8_t> packed((size_t)rows * row_bytes);
+    HIPCHK(hipMemcpy(packed.data(), c->d_ovl_ref, packed.size(), hipMemcpyDeviceToHost));
+    for (int i = 0; i < rows; ++i)
+      unpack_labels(packed.data() + (size_t)i * row_bytes, c->g->n, c->lb,
+                    static_cast<int16_t*>(dst) + (size_t)i * c->g->n);
+    return FW_OK;
+  }
+  const void* src = what == FW_OVERLAP_MATRIX ? (const void*)c->d_ovl_O
+                    : what == FW_OVERLAP_DIST ? (const void*)c->d_ovl_dist
+                                              : (const void*)c->d_ovl_hist;
+  HIPCHK(hipMemcpy(dst, src, need, hipMemcpyDeviceToHost));
+  return FW_OK;
+}
+
+int fw_chains_write_overlap(fw_chains* c, int32_t what, const void* src, size_t bytes) {
+  if (!c) return fail(FW_EINVAL, "fw_chains_write_overlap: null");
+  if (what != FW_OVERLAP_HIST)
+    return fail(FW_EINVAL, "fw_chains_write_overlap: only FW_OVERLAP_HIST can be written (got %d)", what);
+  if (!c->d_ovl_hist)
+    return fail(FW_ESTATE, "fw_chains_write_overlap: neither a reference nor partners are set");
+  size_t need = 0;
+  if (const int rc = ovl_bytes(c, what, &need)) return rc;
+  if (bytes < need || !src) return fail(FW_EINVAL, "the distance histogram needs %zu bytes", need);
+  HIPCHK(hipSetDevice(c->g->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpy(c->d_ovl_hist, src, need, hipMemcpyHostToDevice));
+  return FW_OK;
+}
+
+int fw_chains_overlap_reset(fw_chains* c) {
+  if (!c) return fail(FW_EINVAL, "null handle");
+  if (c->d_ovl_hist) {
+    HIPCHK(hipSetDevice(c->g->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemset(c->d_ovl_hist, 0, ovl_hist_bytes(c, c->n_rungs ? c->n_rungs : 1)));
+  }
+  c->ovl_measured = 0;
+  return FW_OK;
+}
+
+int fw_chains_overlap_info(const fw_chains* c, int64_t info[5]) {
+  if (!c || !info) return fail(FW_EINVAL, "fw_chains_overlap_info: null");
+  info[0] = c->ovl_ref;
+  info[1] = c->lb;
+  info[2] = c->n_rungs ? c->n_rungs : 1;
+  info[3] = c->ovl_partners ? 1 : 0;
+  info[4] = c->ovl_measured;
   return FW_OK;
 }
 

@@ -300,6 +300,37 @@ struct FwGeomHistParams {
   int32_t n_chains, k, n_groups, n_edges;
 };
 
+// ---- plan overlap and Hamming distance (fw_chains_set_reference, fw_overlap.hip) ---------
+#define FW_OVL_MAX_NW 16  // waves (chains) per workgroup at the most
+
+// fw_chains_overlap_async: O[c][d][e] = #{v : R_c(v) = d and X_c(v) = e}, dist[c] = #{v : R_c(v)
+// != X_c(v)}; X_c is the record of chain c, R_c the record of chain partner[c] when partner is
+// set, else the reference row ref + c * ref_stride
+struct FwOverlapParams {
+  const uint8_t* labels;   // packed lb-bit label records, chain c at labels + c * lab_stride
+  int64_t lab_stride;      // bytes, a multiple of 16
+  const uint32_t* ref;     // [1 or n_chains][ref_stride] packed like the records
+  int64_t ref_stride;      // dwords between reference rows, a multiple of 4 (0: one shared row)
+  const int32_t* partner;  // [n_chains] or null (against ref)
+  int64_t* O;              // [n_chains][k][k]
+  int32_t* dist;           // [n_chains]
+  int32_t n_chains, n, k, lb;
+  int32_t lab_words;       // ceil(n lb / 32): the dwords of a record that hold labels
+};
+
+// hist[g][dist[c]] += 1, g = rung[c] (0 without a ladder)
+struct FwOverlapHistParams {
+  const int32_t* dist;       // [n_chains]
+  const int32_t* rung;       // [n_chains] or null
+  unsigned long long* hist;  // [n_groups][n + 1]
+  int32_t n_chains, n_groups, n;
+};
+
+// Host-side launchers implemented in fw_overlap.hip.
+void fw_overlap_plan(int k, int* nw, int* lds_bytes);
+int fw_launch_overlap(const FwOverlapParams& p, int nw, int lds_bytes, void* stream);
+int fw_launch_overlap_hist(const FwOverlapHistParams& h, void* stream);
+
 // Host-side launchers implemented in fw_geometry.hip.
 void fw_geometry_plan(int n, int k, int lb, bool has_w, FwGeomPlan* out);
 int fw_launch_geometry(const FwGeomParams& p, int lds_bytes, void* stream);

@@ -59,6 +59,13 @@ def merge_geometry_hist(hist: np.ndarray, dist=None) -> np.ndarray:
     return allreduce_sum_int64(h.reshape(-1), dist).reshape(h.shape)
 
 
+def merge_distance_hist(hist: np.ndarray, dist=None) -> np.ndarray:
+    """Sum the ranks' plan-distance histograms (``Chains.distance_hist``) with one integer
+    all-reduce: the result is the same array, bit for bit, at any world size."""
+    h = np.ascontiguousarray(hist, np.uint64)
+    return allreduce_sum_int64(h.reshape(-1), dist).reshape(h.shape)
+
+
 def gather_stats(stats: np.ndarray, n_total: int, dist=None, lo: int = 0) -> np.ndarray:
     """Assemble per-chain stats records of all ranks into one [n_total] array (sum-merge)."""
     if dist is None or not dist.is_initialized():

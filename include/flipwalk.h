@@ -514,6 +514,71 @@ int fw_chains_write_geometry(fw_chains* c, int32_t what, const void* src, size_t
 int fw_chains_geometry_reset(fw_chains* c);
 int fw_chains_geometry_info(const fw_chains* c, int64_t info[5]);
 
+/* ---- plan overlap and Hamming distance against snapshots and partner chains ------------
+ * How long a flip chain takes to forget its plan (the question of the reference's paper) is not
+ * visible in the cut count: a chain whose cut has long decorrelated can still hold every
+ * district where the seed put it.  An overlap compares every chain's current plan X_c with a
+ * reference plan R_c, node by node, on the device and between launches, as the exchange, record,
+ * tally and geometry steps are placed; no run kernel changes.  Every result is an exact integer
+ * count of nodes; the scores are formed on the host (plandist.py).
+ *
+ * fw_chains_set_reference, labels == NULL: a snapshot.  Enqueues on the handle's stream, with no
+ * host synchronisation, a device-to-device copy of the label words of every chain's record into
+ * a reference buffer the handle owns; the reference becomes per-chain and is the plans at that
+ * point of the stream.  labels != NULL: int16 [1][n] (per_chain 0, one plan shared by every
+ * chain) or [n_chains][n] (per_chain 1), every value in [0, k), else FW_EINVAL, checked on the
+ * host before the device is touched; a reference may be any labelling (it need not be
+ * contiguous or balanced).  Either form replaces the reference, zeroes the histogram and
+ * n_measured and invalidates MATRIX and DIST.
+ *
+ * fw_chains_set_partners: partner int32 [n_chains], every value in [0, n_chains), else
+ * FW_EINVAL, checked on the host first; partner[c] == c is allowed (distance 0).  The array is
+ * kept on the device; the histogram is not touched.
+ *
+ * fw_chains_overlap_async (FW_ESTATE for FW_OVERLAP_REFERENCE without a reference and for
+ * FW_OVERLAP_PARTNER without partners, FW_EINVAL for another value) enqueues on the handle's
+ * stream, with no host synchronisation and without touching fw_chains_last_kernel_ms, for every
+ * chain c (stuck chains like any other), with R_c the stored reference (REFERENCE) or the
+ * current plan of chain partner[c] (PARTNER; the kernel only reads the plans, so the order of
+ * the chains cannot matter):
+ *   O[c][d][e] = #{v : R_c(v) = d and X_c(v) = e}    (row sums: the reference's district sizes,
+ *                column sums: the current ones, total n)
+ *   dist[c]    = #{v : R_c(v) != X_c(v)} = n - trace(O[c])
+ *   hist[g][dist[c]] += 1, g = the chain's current rung under a ladder, else 0.
+ * The host counter n_measured is incremented at enqueue.  O and dist are plain vector stores
+ * from one owner each (no global atomics, no dependence on thread order); the histogram is
+ * accumulated with integer atomics, whose sum does not depend on the order.
+ *
+ * fw_chains_read_overlap synchronises, then copies
+ *   FW_OVERLAP_MATRIX  int64  [n_chains][k][k]      of the last measurement
+ *   FW_OVERLAP_DIST    int32  [n_chains]            of the last measurement
+ *   FW_OVERLAP_HIST    uint64 [n_groups][n + 1]     accumulated over all measurements;
+ *                                                   n_groups = n_rungs, or 1 without a ladder
+ *   FW_OVERLAP_REF     int16  [1 or n_chains][n]    the stored reference, unpacked (checkpoints)
+ * FW_ESTATE before any reference or partners were set, for REF without a reference, and for
+ * MATRIX / DIST when the last measurement does not stand: nothing was measured since the
+ * reference was set, or the last measurement was against partners that have been replaced
+ * since.  FW_EINVAL for a buffer that is too small.  fw_chains_write_overlap restores
+ * FW_OVERLAP_HIST only (checkpoints; n_measured is not changed); fw_chains_overlap_reset zeroes
+ * the histogram and n_measured.  fw_chains_overlap_info: info = {reference kind (0 none,
+ * 1 shared, 2 per chain), label bits per node of the handle's plans, n_groups, partners set
+ * (0 / 1), n_measured}.  fw_chains_reset_observables leaves all of this alone;
+ * fw_chains_set_ladder re-sizes the histogram for the new group count and zeroes it.  (These
+ * entry points arrived in 0.7 without a version bump.) */
+#define FW_OVERLAP_REFERENCE 0   /* against the stored reference          */
+#define FW_OVERLAP_PARTNER   1   /* against the current plan of partner[c] */
+#define FW_OVERLAP_MATRIX 0      /* int64  [n_chains][k][k]  last measurement */
+#define FW_OVERLAP_DIST   1      /* int32  [n_chains]        last measurement */
+#define FW_OVERLAP_HIST   2      /* uint64 [n_groups][n + 1] accumulated      */
+#define FW_OVERLAP_REF    3      /* int16  [1 or n_chains][n] the stored reference */
+int fw_chains_set_reference(fw_chains* c, const int16_t* labels, int32_t per_chain);
+int fw_chains_set_partners(fw_chains* c, const int32_t* partner /*[n_chains]*/);
+int fw_chains_overlap_async(fw_chains* c, int32_t against);
+int fw_chains_read_overlap(fw_chains* c, int32_t what, void* dst, size_t bytes);
+int fw_chains_write_overlap(fw_chains* c, int32_t what, const void* src, size_t bytes);
+int fw_chains_overlap_reset(fw_chains* c);
+int fw_chains_overlap_info(const fw_chains* c, int64_t info[5]);
+
 /* Read a map (FW_MAP_*) of chains [chain0, chain0 + n_chains) as int64
  * [n_chains][len], or with FW_MAP_SUM its sum over those chains [len]; len is
  * n_edges for FW_MAP_CUT_TIMES and n otherwise.  Values are current through the
