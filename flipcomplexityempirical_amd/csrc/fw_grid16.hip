@@ -27,6 +27,7 @@
 #include <algorithm>
 
 #include "fw_device.h"
+#include "fw_weights_bytes.h"
 #include "fw_window_rows.h"
 
 #ifdef FW_STAMPS
@@ -308,14 +309,43 @@ __device__ __forceinline__ void weights4_swar(const LDS uint8_t* lab, int x0, in
   }
 }
 
-// weights (and, when NEED_CD, cut degrees) of nodes x0..x0+3, one per byte
+// The byte form of weights4_swar for W4 grids (fw_weights_bytes.h): row-lane q's four nodes
+// of group gi are one label byte, so the lane reads four bytes -- its own, the ones W/4
+// before and after, and the group's edge byte (row-lanes 0 and 15) -- all issued before any
+// is used, and takes the left / right neighbours from the adjacent lanes' one-hot words
+// (row_shr:1 / row_shl:1; lanes 0 and 15 keep `old`, the edge byte's field).  No read leaves
+// the lane's slot or the guard in front of it: wb_offsets states the bounds.  Runs with every
+// lane active.  No sched_barrier behind the reads (weights4_swar's BATCH): four byte reads
+// stay together without one, and C3 measured 0.1% faster without it.
+template <int MODE, bool NEED_CD>
+__device__ __forceinline__ void weights4_bytes(const LDS uint8_t* lab, int gi, int q, int W, int H,
+                                               int n, GDiv gd, uint32_t& w4, uint32_t& cd4) {
+  const int x0 = gi * 64 + q * 4;
+  const int r0 = gd(x0);
+  const int c0 = x0 - mulW(r0, W);
+  int own, up, dn, edge;
+  wb_offsets(gi, q, r0, W, H, own, up, dn, edge);
+  const uint32_t bo = lab[own], bu = lab[up], bd = lab[dn], be = lab[edge];
+  uint32_t mN, mU, mD, mL, mR;
+  wb_masks(x0, r0, c0, W, H, n, mN, mU, mD, mL, mR);
+  const uint32_t O = wb_onehot(bo), U = wb_onehot(bu), Dn = wb_onehot(bd);
+  const uint32_t E = wb_edge(be, q);
+  const uint32_t Oprev = (uint32_t)__builtin_amdgcn_update_dpp((int)E, (int)O, 0x111, 0xF, 0xF, false);
+  const uint32_t Onext = (uint32_t)__builtin_amdgcn_update_dpp((int)E, (int)O, 0x101, 0xF, 0xF, false);
+  wb_weights<MODE == FW_PROPOSE_CUTEDGE, NEED_CD>(O, U, Dn, Oprev, Onext, mN, mU, mD, mL, mR, w4, cd4);
+}
+
+// weights (and, when NEED_CD, cut degrees) of the four nodes of row-lane q in group gi
+// (64 gi + 4 q ..), one per byte
 template <int LB, int MODE, bool NEED_CD, bool BATCH = true, bool W4 = false>
-__device__ __forceinline__ void weights4x(const LDS uint8_t* lab, int x0, int W, int H, int n,
+__device__ __forceinline__ void weights4x(const LDS uint8_t* lab, int gi, int q, int W, int H, int n,
                                           GDiv gd, uint32_t& w4, uint32_t& cd4) {
-  if constexpr (LB == 2)
-    weights4_swar<MODE, NEED_CD, BATCH, W4>(lab, x0, W, H, n, gd, w4, cd4);
+  if constexpr (LB == 2 && W4)
+    weights4_bytes<MODE, NEED_CD>(lab, gi, q, W, H, n, gd, w4, cd4);
+  else if constexpr (LB == 2)
+    weights4_swar<MODE, NEED_CD, BATCH, false>(lab, gi * 64 + q * 4, W, H, n, gd, w4, cd4);
   else
-    weights4<LB, MODE>(lab, x0, W, H, n, gd, w4, cd4);
+    weights4<LB, MODE>(lab, gi * 64 + q * 4, W, H, n, gd, w4, cd4);
 }
 
 // bytes of w (each < 64) summed
@@ -785,7 +815,7 @@ __device__ __forceinline__ void grid16_body(const FwRunParams& p) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           uint32_t w4, cd4;
-          weights4x<LB, MODE, true, true, W4>(lab, (2 * t2 + h) * 64 + q * 4, W, H, n, gd, w4, cd4);
+          weights4x<LB, MODE, true, true, W4>(lab, 2 * t2 + h, q, W, H, n, gd, w4, cd4);
           const uint32_t ws = bsum4m(w4);
           cut2 += bsum4m(cd4);
           bn += ((cd4 & 0xFFu) != 0) + ((cd4 & 0xFF00u) != 0) + ((cd4 & 0xFF0000u) != 0) +
@@ -1059,9 +1089,8 @@ __device__ __forceinline__ void grid16_body(const FwRunParams& p) {
 
       STAMP(1);  // level 1
       // ---- select, level 2: weights of the group's 64 nodes, 4 per lane
-      const int x0 = gi * 64 + q * 4;
       uint32_t w4, cd4;  // four 8-bit weights
-      weights4x<LB, MODE, false, !W2, W4>(lab, x0, W, H, n, gd, w4, cd4);
+      weights4x<LB, MODE, false, !W2, W4>(lab, gi, q, W, H, n, gd, w4, cd4);
       // byte t: weights of nodes 0..t (<= 16); two shift-adds, not a quarter-rate multiply
       const uint32_t pref1 = w4 + (w4 << 8);
       const uint32_t pref = pref1 + (pref1 << 16);
