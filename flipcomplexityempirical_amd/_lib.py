@@ -30,6 +30,8 @@ TALLY_MAX_COLS, TALLY_MAX_ELECTIONS = 8, 4
 GEOM_DISTRICTS, GEOM_HIST = 0, 1
 OVERLAP_REFERENCE, OVERLAP_PARTNER = 0, 1
 OVERLAP_MATRIX, OVERLAP_DIST, OVERLAP_HIST, OVERLAP_REF = 0, 1, 2, 3
+RESAMPLE_SRC, RESAMPLE_FAMILY, RESAMPLE_WEIGHTS = 0, 1, 2
+RESAMPLE_MAX_CHAINS = 1 << 20
 
 STATS_DTYPE = np.dtype(
     [
@@ -126,6 +128,11 @@ SIGNATURES = [
     ("fw_chains_write_overlap", ctypes.c_int, [_P, _I32, _P, ctypes.c_size_t]),
     ("fw_chains_overlap_reset", ctypes.c_int, [_P]),
     ("fw_chains_overlap_info", ctypes.c_int, [_P, _P]),
+    ("fw_chains_clone_async", ctypes.c_int, [_P, _P]),
+    ("fw_chains_resample_async", ctypes.c_int, [_P, _P, _I32, _I64]),
+    ("fw_chains_resample_info", ctypes.c_int, [_P, _P]),
+    ("fw_chains_read_resample", ctypes.c_int, [_P, _I32, _P, ctypes.c_size_t]),
+    ("fw_chains_write_resample", ctypes.c_int, [_P, _I32, _P, ctypes.c_size_t]),
     ("fw_chains_read_map", ctypes.c_int, [_P, _I32, _I32, _I32, _I32, _P, ctypes.c_size_t]),
     ("fw_eval_flips", ctypes.c_int,
      [_P, _P, _I32, _P, _P, _I32, _I64, _I64, _P, _P, _P, _P]),

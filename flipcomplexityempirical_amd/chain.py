@@ -275,6 +275,10 @@ class Chains:
         # handle); _overlap_base as _tally_base
         self.partners = None
         self._overlap_base = 0
+        # clone / resample: the round the next resample() takes by default, and the counts a
+        # restored checkpoint started from (as _tally_base)
+        self.resample_round = 0
+        self._resample_base, self._clone_base = 0, 0
         h = _lib.ctypes.c_void_p()
         check(L.fw_chains_create(dgraph.handle, self.n_chains, self.k, ptr(lab), per_chain,
                                  self.mode, self.pop_lo, self.pop_hi, ptr(self.thr), thr_per,
@@ -750,6 +754,97 @@ class Chains:
         check(_lib.load().fw_chains_overlap_reset(self._h))
         self._overlap_base = 0
 
+    # ------------------------------------------------------------- resampling across chains
+    def clone(self, src) -> None:
+        """Chain i continues from the current plan of chain ``src[i]`` (fw_chains_clone_async):
+        int [n_chains], every value in [0, n_chains) and every source a fixed point
+        (``src[src[i]] == src[i]``).  The plan moves (labels, populations, cut / bnodes / npairs
+        / stuck, flagged-node counts, the current sampled wait, the family); the chain stays
+        (its Philox counter, sums, counters, thr row, series).  Enqueued on the handle's stream
+        behind the runs already there; no wait."""
+        a = np.asarray(src)
+        if a.dtype.kind not in "iu" or a.shape != (self.n_chains,):
+            raise ValueError(f"src must be integers [{self.n_chains}]")
+        a = np.ascontiguousarray(a, np.int32)
+        check(_lib.load().fw_chains_clone_async(self._h, ptr(a)))
+
+    def resample(self, base_from: float, base_to: float, round: Optional[int] = None) -> None:
+        """One systematic resampling of the population for the change of base ``base_from`` ->
+        ``base_to`` (fw_chains_resample_async with ``population.weight_table``): chains are
+        re-weighted by (base_to / base_from) ** (-cut), the source map is drawn on the device and
+        applied as ``clone``.  The draw is a function of (seed, chain_id0, round); ``round``
+        defaults to ``resample_round``, which then advances.  No wait."""
+        from .population import weight_table
+        q, sign = weight_table(base_from, base_to, self.dgraph.n_edges)
+        r = self.resample_round if round is None else int(round)
+        check(_lib.load().fw_chains_resample_async(self._h, ptr(q), sign, r))
+        self.resample_round = r + 1
+
+    def resample_info(self) -> dict:
+        """Waits for the stream; the counters and the integer sums of the last resample."""
+        info = np.zeros(8, np.int64)
+        check(_lib.load().fw_chains_resample_info(self._h, ptr(info)))
+        return {"n_resampled": int(info[0]) + self._resample_base, "round": int(info[1]),
+                "T": int(info[2]), "S2": int(info[3]), "cref": int(info[4]),
+                "survivors": int(info[5]), "max_offspring": int(info[6]),
+                "clones": int(info[7]) + self._clone_base}
+
+    def _read_resample(self, what, dtype):
+        arr = np.empty(self.n_chains, dtype)
+        check(_lib.load().fw_chains_read_resample(self._h, what, ptr(arr), arr.nbytes))
+        return arr
+
+    def families(self) -> np.ndarray:
+        """int32 [n_chains]: the chain whose initial plan each current plan descends from."""
+        return self._read_resample(_lib.RESAMPLE_FAMILY, np.int32)
+
+    def last_sources(self) -> np.ndarray:
+        """int32 [n_chains]: the last map, of ``clone`` or ``resample``."""
+        return self._read_resample(_lib.RESAMPLE_SRC, np.int32)
+
+    def last_weights(self) -> np.ndarray:
+        """uint32 [n_chains]: the weights of the last ``resample`` (the heaviest: 2^30)."""
+        return self._read_resample(_lib.RESAMPLE_WEIGHTS, np.uint32)
+
+    def run_annealed(self, bases, steps_per_stage: int, resample: bool = True,
+                     record: bool = False, tally: bool = False, geometry: bool = False,
+                     overlap: bool | str = False, max_retries: int = DEFAULT_MAX_RETRIES,
+                     estimate: bool = True):
+        """Population annealing over ``bases``: at stage s every chain's bound table becomes
+        that of ``bases[s]`` (a one-row ``set_schedule``, which stays in force afterwards), the
+        population is resampled from ``bases[s - 1]`` (s >= 1, with ``resample``) and runs
+        ``steps_per_stage`` steps; then tally, geometry, overlap, record as asked.  The
+        population is taken to sit at ``bases[0]`` on entry.  With ``estimate`` each stage's
+        ``resample_info`` is read (one wait per stage) and the result is {"log_weight": the
+        stages' ``population.log_weight_mean``, "log_z": their sum, "ess": the stages' effective
+        sample sizes}; without it the resamples and runs are enqueued back to back, the tables'
+        ``set_schedule`` calls being the only waits, and None is returned."""
+        from .population import effective_sample_size, log_weight_mean
+        bases = [float(b) for b in np.asarray(bases, np.float64).ravel()]
+        D = self.dgraph.maxdeg
+        logw, ess = [], []
+        for s, b in enumerate(bases):
+            self.set_schedule(metropolis_table(b, D)[None, :])
+            if s and resample:
+                self.resample(bases[s - 1], b)
+                if estimate:
+                    info = self.resample_info()
+                    logw.append(log_weight_mean(info, bases[s - 1], b, self.n_chains))
+                    ess.append(effective_sample_size(info))
+            self.run_async(int(steps_per_stage), max_retries)
+            if tally:
+                self.tally()
+            if geometry:
+                self.geometry()
+            if overlap:
+                self.overlap("reference" if overlap is True else overlap)
+            if record:
+                self.record()
+        self.sync()
+        if not (estimate and resample):
+            return None
+        return {"log_weight": np.array(logw), "log_z": float(np.sum(logw)), "ess": np.array(ess)}
+
     # ------------------------------------------------------------- sampled waits
     def enable_sampled_waits(self) -> None:
         """Draw geom_wait per state object (grid_chain_sec11.py:147-148, cached and re-used
@@ -853,6 +948,11 @@ class Chains:
                 ck["overlap_partners"] = self.partners
             ck["distance_hist"] = self.distance_hist()
             ck["n_overlaps"] = np.int64(ovl["n_measured"])
+        rsm = self.resample_info()
+        if rsm["clones"] or rsm["n_resampled"] or self.resample_round:
+            ck["families"] = self.families()
+            ck["n_resampled"], ck["n_clones"] = np.int64(rsm["n_resampled"]), np.int64(rsm["clones"])
+            ck["resample_round"] = np.int64(self.resample_round)
         return ck
 
     def restore(self, ck: dict) -> None:
@@ -967,6 +1067,16 @@ class Chains:
             # the handle's own count went on unless a reference was set just now
             self._overlap_base = int(ck["n_overlaps"]) - (self.overlap_info()["n_measured"] -
                                                           self._overlap_base)
+        # the families and the resample counters (the handle's own counts went on)
+        if "families" in ck:
+            a = np.ascontiguousarray(ck["families"], np.int32)
+            if a.shape != (self.n_chains,):
+                raise ValueError("checkpoint of another chain count")
+            check(L.fw_chains_write_resample(self._h, _lib.RESAMPLE_FAMILY, ptr(a), a.nbytes))
+            now = self.resample_info()
+            self._resample_base += int(ck["n_resampled"]) - now["n_resampled"]
+            self._clone_base += int(ck["n_clones"]) - now["clones"]
+            self.resample_round = int(ck["resample_round"])
 
     def save_checkpoint(self, path: str) -> None:
         ck = self.checkpoint()

@@ -16,6 +16,7 @@
 
 #include "fw_internal.h"
 #include "fw_math.h"
+#include "fw_resample_limbs.h"
 
 namespace {
 
@@ -223,6 +224,24 @@ struct fw_chains {
   int64_t* d_ovl_O = nullptr;         // [n_chains][k][k]
   int32_t* d_ovl_dist = nullptr;      // [n_chains]
   unsigned long long* d_ovl_hist = nullptr;  // [n_groups][n + 1], the group count in force
+  // fw_chains_clone_async / fw_chains_resample_async; FwCloneParams / FwResampleParams name the
+  // arrays (allocated by the first call; d_rsm_family == nullptr: every family is its own chain)
+  int64_t n_resampled = 0, rsm_round = -1, rsm_host_clones = 0;
+  bool rsm_have_src = false, rsm_have_w = false;  // a map / a resample's weights exist
+  int32_t* d_rsm_src = nullptr;
+  int32_t* d_rsm_family = nullptr;
+  uint32_t* d_rsm_q = nullptr;     // [n_edges + 1]
+  uint32_t* d_rsm_w = nullptr;
+  uint64_t* d_rsm_cum = nullptr;
+  uint64_t* d_rsm_pts = nullptr;
+  int32_t* d_rsm_lower = nullptr;
+  int32_t* d_rsm_extra = nullptr;
+  int64_t* d_rsm_info = nullptr;   // [8]
+  // uploads without a host wait: two pinned staging slots, each with the event of its last copy
+  void* rsm_stage[2] = {nullptr, nullptr};
+  hipEvent_t rsm_ev[2] = {nullptr, nullptr};
+  int rsm_slot = 0;
+  std::vector<uint32_t> rsm_q;     // the table d_rsm_q holds (an equal table is not uploaded again)
 };
 
 namespace {
@@ -547,9 +566,15 @@ void fw_chains_destroy(fw_chains* c) {
                   c->d_ser_cut, c->d_ser_bn, c->d_ser_rung,
                   c->d_tal_cols, c->d_tal_sums, c->d_tal_seats, c->d_tal_hist,
                   c->d_geo_w, c->d_geo_area, c->d_geo_ext, c->d_geo_out, c->d_geo_hist,
-                  c->d_ovl_ref, c->d_ovl_partner, c->d_ovl_O, c->d_ovl_dist, c->d_ovl_hist};
+                  c->d_ovl_ref, c->d_ovl_partner, c->d_ovl_O, c->d_ovl_dist, c->d_ovl_hist,
+                  c->d_rsm_src, c->d_rsm_family, c->d_rsm_q, c->d_rsm_w, c->d_rsm_cum, c->d_rsm_pts,
+                  c->d_rsm_lower, c->d_rsm_extra, c->d_rsm_info};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
+  for (int i = 0; i < 2; ++i) {
+    if (c->rsm_stage[i]) (void)hipHostFree(c->rsm_stage[i]);
+    if (c->rsm_ev[i]) (void)hipEventDestroy(c->rsm_ev[i]);
+  }
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -2321,6 +2346,223 @@ int fw_chains_overlap_info(const fw_chains* c, int64_t info[5]) {
   info[2] = c->n_rungs ? c->n_rungs : 1;
   info[3] = c->ovl_partners ? 1 : 0;
   info[4] = c->ovl_measured;
+  return FW_OK;
+}
+
+// ---------------------------------------------------------------- resampling across chains
+namespace {
+
+size_t rsm_stage_bytes(const fw_chains* c) {
+  return sizeof(uint32_t) * std::max((size_t)c->n_chains, (size_t)(c->g->nnz / 2 + 1));
+}
+
+// the buffers every resample entry point shares, allocated by the first clone or resample (the
+// families start as the identity); on failure the handle keeps what it had
+int rsm_ensure(fw_chains* c) {
+  if (c->d_rsm_family) return FW_OK;
+  const size_t C = (size_t)c->n_chains;
+  void* nb[9] = {};
+  const size_t sz[9] = {sizeof(int32_t) * C,  sizeof(int32_t) * C,  sizeof(uint32_t) * (size_t)(c->g->nnz / 2 + 1),
+                        sizeof(uint32_t) * C, sizeof(uint64_t) * C, sizeof(uint64_t) * C,
+                        sizeof(int32_t) * C,  sizeof(int32_t) * C,  sizeof(int64_t) * 8};
+  void* st[2] = {};
+  hipEvent_t ev[2] = {};
+  bool ok = true;
+  for (int i = 0; i < 9 && ok; ++i) ok = hipMalloc(&nb[i], sz[i]) == hipSuccess;
+  for (int i = 0; i < 2 && ok; ++i)
+    ok = hipHostMalloc(&st[i], rsm_stage_bytes(c), hipHostMallocDefault) == hipSuccess &&
+         hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) == hipSuccess;
+  std::vector<int32_t> iota(C);
+  for (size_t i = 0; i < C; ++i) iota[i] = (int32_t)i;
+  const bool up = ok && hipMemcpy(nb[1], iota.data(), sz[1], hipMemcpyHostToDevice) == hipSuccess &&
+                  hipMemset(nb[8], 0, sz[8]) == hipSuccess;
+  if (!up) {
+    for (void* b : nb)
+      if (b) (void)hipFree(b);
+    for (int i = 0; i < 2; ++i) {
+      if (st[i]) (void)hipHostFree(st[i]);
+      if (ev[i]) (void)hipEventDestroy(ev[i]);
+    }
+    (void)hipGetLastError();
+    return ok ? fail(FW_EHIP, "resample buffers could not be initialised")
+              : fail(FW_ENOMEM, "resample buffers of %d chains", c->n_chains);
+  }
+  c->d_rsm_src = static_cast<int32_t*>(nb[0]);
+  c->d_rsm_family = static_cast<int32_t*>(nb[1]);
+  c->d_rsm_q = static_cast<uint32_t*>(nb[2]);
+  c->d_rsm_w = static_cast<uint32_t*>(nb[3]);
+  c->d_rsm_cum = static_cast<uint64_t*>(nb[4]);
+  c->d_rsm_pts = static_cast<uint64_t*>(nb[5]);
+  c->d_rsm_lower = static_cast<int32_t*>(nb[6]);
+  c->d_rsm_extra = static_cast<int32_t*>(nb[7]);
+  c->d_rsm_info = static_cast<int64_t*>(nb[8]);
+  for (int i = 0; i < 2; ++i) {
+    c->rsm_stage[i] = st[i];
+    c->rsm_ev[i] = ev[i];
+  }
+  return FW_OK;
+}
+
+// host array -> device array on the handle's stream through a pinned slot: the host waits only
+// for the copy that used the slot two uploads ago, never for the stream
+int rsm_upload(fw_chains* c, void* dst, const void* src, size_t bytes) {
+  const int s = c->rsm_slot;
+  c->rsm_slot ^= 1;
+  HIPCHK(hipEventSynchronize(c->rsm_ev[s]));
+  std::memcpy(c->rsm_stage[s], src, bytes);
+  HIPCHK(hipMemcpyAsync(dst, c->rsm_stage[s], bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipEventRecord(c->rsm_ev[s], c->stream));
+  return FW_OK;
+}
+
+// what both entry points refuse (include/flipwalk.h)
+int rsm_refuse(const fw_chains* c, const char* who) {
+  if (c->d_acc)
+    return fail(FW_ESTATE, "%s: plans cannot be moved while the spatial maps are enabled", who);
+  if (c->n_rungs)
+    return fail(FW_EUNSUPPORTED, "%s: a laddered handle's chains are not resampled", who);
+  return FW_OK;
+}
+
+int rsm_launch_clone(fw_chains* c) {
+  FwCloneParams p{};
+  p.labels = c->d_labels;
+  p.lab_stride = c->p.lab_stride;
+  p.stats = c->d_stats;
+  p.pops = c->d_pops;
+  p.bcnt = c->p.bcnt;
+  p.wsamp = c->d_wsamp;
+  p.src = c->d_rsm_src;
+  p.family = c->d_rsm_family;
+  p.n_chains = c->n_chains;
+  p.k = c->k;
+  // the copied record, its group sums and the three copied counts stay consistent with each
+  // other, so the derived-state cache stays as it was; the run timing events are left alone
+  const int le = fw_launch_clone(p, c->stream);
+  if (le != 0) return fail(FW_EHIP, "clone launch failed: %s", hipGetErrorString((hipError_t)le));
+  c->rsm_have_src = true;
+  return FW_OK;
+}
+
+}  // namespace
+
+int fw_chains_clone_async(fw_chains* c, const int32_t* src) {
+  if (!c || !src) return fail(FW_EINVAL, "fw_chains_clone_async: null");
+  const int C = c->n_chains;
+  int64_t moved = 0;
+  for (int i = 0; i < C; ++i) {
+    if (src[i] < 0 || src[i] >= C)
+      return fail(FW_EINVAL, "source %d of chain %d outside [0, %d)", src[i], i, C);
+    if (src[src[i]] != src[i])
+      return fail(FW_EINVAL, "source %d of chain %d is not a fixed point (its own source is %d)",
+                  src[i], i, src[src[i]]);
+    moved += src[i] != i;
+  }
+  if (const int rc = rsm_refuse(c, "fw_chains_clone_async")) return rc;
+  HIPCHK(hipSetDevice(c->g->device));
+  if (const int rc = rsm_ensure(c)) return rc;
+  if (const int rc = rsm_upload(c, c->d_rsm_src, src, sizeof(int32_t) * (size_t)C)) return rc;
+  if (const int rc = rsm_launch_clone(c)) return rc;
+  c->rsm_host_clones += moved;
+  return FW_OK;
+}
+
+int fw_chains_resample_async(fw_chains* c, const uint32_t* q, int32_t sign, int64_t round) {
+  if (!c || !q) return fail(FW_EINVAL, "fw_chains_resample_async: null");
+  const int E = c->g->nnz / 2;
+  if (sign != 1 && sign != -1) return fail(FW_EINVAL, "sign = %d is neither +1 nor -1", sign);
+  if (round < 0 || round > 0xFFFFFFFFll)
+    return fail(FW_EINVAL, "round %lld outside [0, 2^32)", (long long)round);
+  if (q[0] != FW_RSM_ONE) return fail(FW_EINVAL, "q[0] = %u is not 2^30", q[0]);
+  for (int d = 1; d <= E; ++d)
+    if (q[d] > q[d - 1]) return fail(FW_EINVAL, "q[%d] = %u > q[%d] = %u: the table must not increase", d, q[d], d - 1, q[d - 1]);
+  if (c->n_chains > FW_RSM_MAX_CHAINS)
+    return fail(FW_EUNSUPPORTED, "%d chains > 2^20: the points' limb arithmetic stops there", c->n_chains);
+  if (const int rc = rsm_refuse(c, "fw_chains_resample_async")) return rc;
+  HIPCHK(hipSetDevice(c->g->device));
+  if (const int rc = rsm_ensure(c)) return rc;
+  if (c->rsm_q.size() != (size_t)E + 1 || std::memcmp(c->rsm_q.data(), q, sizeof(uint32_t) * ((size_t)E + 1))) {
+    c->rsm_q.clear();  // nothing is cached should the upload fail
+    if (const int rc = rsm_upload(c, c->d_rsm_q, q, sizeof(uint32_t) * ((size_t)E + 1))) return rc;
+    c->rsm_q.assign(q, q + E + 1);
+  }
+  FwResampleParams r{};
+  r.stats = c->d_stats;
+  r.q = c->d_rsm_q;
+  r.w = c->d_rsm_w;
+  r.cum = c->d_rsm_cum;
+  r.pts = c->d_rsm_pts;
+  r.lower = c->d_rsm_lower;
+  r.extra = c->d_rsm_extra;
+  r.src = c->d_rsm_src;
+  r.info = c->d_rsm_info;
+  r.n_chains = c->n_chains;
+  r.n_edges = E;
+  r.sign = sign;
+  r.round = (uint32_t)round;
+  r.seed = c->p.seed;
+  r.chain_id0 = c->p.chain_id0;
+  const int le = fw_launch_resample_map(r, c->stream);
+  if (le != 0) return fail(FW_EHIP, "resample launch failed: %s", hipGetErrorString((hipError_t)le));
+  c->rsm_have_w = true;
+  if (const int rc = rsm_launch_clone(c)) return rc;
+  c->n_resampled += 1;
+  c->rsm_round = round;
+  return FW_OK;
+}
+
+int fw_chains_resample_info(fw_chains* c, int64_t info[8]) {
+  if (!c || !info) return fail(FW_EINVAL, "fw_chains_resample_info: null");
+  int64_t dev[8] = {};
+  if (c->d_rsm_info) {
+    HIPCHK(hipSetDevice(c->g->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(dev, c->d_rsm_info, sizeof dev, hipMemcpyDeviceToHost));
+  }
+  info[0] = c->n_resampled;
+  info[1] = c->rsm_round;
+  for (int i = 0; i < 5; ++i) info[2 + i] = dev[i];
+  info[7] = dev[5] + c->rsm_host_clones;
+  return FW_OK;
+}
+
+int fw_chains_read_resample(fw_chains* c, int32_t what, void* dst, size_t bytes) {
+  if (!c) return fail(FW_EINVAL, "fw_chains_read_resample: null");
+  if (what != FW_RESAMPLE_SRC && what != FW_RESAMPLE_FAMILY && what != FW_RESAMPLE_WEIGHTS)
+    return fail(FW_EINVAL, "unknown resample kind %d", what);
+  if (what == FW_RESAMPLE_SRC && !c->rsm_have_src)
+    return fail(FW_ESTATE, "fw_chains_read_resample: nothing has been cloned or resampled yet");
+  if (what == FW_RESAMPLE_WEIGHTS && !c->rsm_have_w)
+    return fail(FW_ESTATE, "fw_chains_read_resample: nothing has been resampled yet");
+  const size_t need = 4 * (size_t)c->n_chains;
+  if (bytes < need || !dst) return fail(FW_EINVAL, "the resample array needs %zu bytes", need);
+  if (!c->d_rsm_family) {  // FAMILY of a handle that never cloned
+    for (int i = 0; i < c->n_chains; ++i) static_cast<int32_t*>(dst)[i] = i;
+    return FW_OK;
+  }
+  HIPCHK(hipSetDevice(c->g->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const void* src = what == FW_RESAMPLE_SRC      ? (const void*)c->d_rsm_src
+                    : what == FW_RESAMPLE_FAMILY ? (const void*)c->d_rsm_family
+                                                 : (const void*)c->d_rsm_w;
+  HIPCHK(hipMemcpy(dst, src, need, hipMemcpyDeviceToHost));
+  return FW_OK;
+}
+
+int fw_chains_write_resample(fw_chains* c, int32_t what, const void* src, size_t bytes) {
+  if (!c) return fail(FW_EINVAL, "fw_chains_write_resample: null");
+  if (what != FW_RESAMPLE_FAMILY)
+    return fail(FW_EINVAL, "fw_chains_write_resample: only FW_RESAMPLE_FAMILY can be written (got %d)", what);
+  const size_t need = sizeof(int32_t) * (size_t)c->n_chains;
+  if (bytes < need || !src) return fail(FW_EINVAL, "the families need %zu bytes", need);
+  const int32_t* f = static_cast<const int32_t*>(src);
+  for (int i = 0; i < c->n_chains; ++i)
+    if (f[i] < 0 || f[i] >= c->n_chains)
+      return fail(FW_EINVAL, "family %d of chain %d outside [0, %d)", f[i], i, c->n_chains);
+  HIPCHK(hipSetDevice(c->g->device));
+  if (const int rc = rsm_ensure(c)) return rc;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpy(c->d_rsm_family, src, need, hipMemcpyHostToDevice));
   return FW_OK;
 }
 

@@ -326,6 +326,46 @@ struct FwOverlapHistParams {
   int32_t n_chains, n_groups, n;
 };
 
+// ---- resampling plans across chains (fw_chains_clone_async, fw_resample.hip) ---------------
+#define FW_RSM_THREADS 1024  // the one workgroup of the map kernel
+#define FW_RSM_CLONE_NW 4    // waves (destination chains) per workgroup of the gather
+
+// fw_chains_clone_async: chain i takes the plan of chain src[i] (a fixed point of src); what
+// describes the plan moves, what describes the chain stays (include/flipwalk.h)
+struct FwCloneParams {
+  uint8_t* labels;        // label records, chain c at labels + c * lab_stride
+  int64_t lab_stride;     // bytes, a multiple of 16
+  fw_chain_stats* stats;  // [n_chains]: cut, bnodes, npairs, stuck move
+  int64_t* pops;          // [n_chains][k]
+  int32_t* bcnt;          // [n_chains][k] or null (FW_ACCEPT_BOUNDARY's flagged-node counts)
+  double* wsamp;          // [n_chains][2] or null: the current state's draw [1] moves
+  const int32_t* src;     // [n_chains]
+  int32_t* family;        // [n_chains]
+  int32_t n_chains, k;
+};
+
+// fw_chains_resample_async: the source map of one systematic resampling by cut.  info =
+// {T, S2, cref, survivors, max offspring, clones (accumulated over the handle's resamples), u, -}
+struct FwResampleParams {
+  const fw_chain_stats* stats;  // [n_chains]
+  const uint32_t* q;            // [n_edges + 1]
+  uint32_t* w;                  // [n_chains] weights
+  uint64_t* cum;                // [n_chains] inclusive prefix sums of w
+  uint64_t* pts;                // [n_chains] the points p_j
+  int32_t* lower;               // [n_chains] #{j : p_j < cum[i]}
+  int32_t* extra;               // [n_chains] inclusive prefix sums of max(offspring - 1, 0)
+  int32_t* src;                 // [n_chains] the map
+  int64_t* info;                // [8]
+  int32_t n_chains, n_edges, sign;
+  uint32_t round;
+  uint64_t seed;
+  int64_t chain_id0;
+};
+
+// Host-side launchers implemented in fw_resample.hip.
+int fw_launch_clone(const FwCloneParams& p, void* stream);
+int fw_launch_resample_map(const FwResampleParams& p, void* stream);
+
 // Host-side launchers implemented in fw_overlap.hip.
 void fw_overlap_plan(int k, int* nw, int* lds_bytes);
 int fw_launch_overlap(const FwOverlapParams& p, int nw, int lds_bytes, void* stream);

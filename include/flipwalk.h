@@ -171,7 +171,8 @@ int32_t fw_version(void);
 /* Provenance of this build (static string, never NULL): "src=<sha256 of the flip
  * kernels, headers and ABI source> flags=<compiler flags, including any -D>
  * series=<sha256 of fw_series.hip> tally=<sha256 of fw_tally.hip> geom=<sha256 of
- * fw_geometry.hip> win=<sha256 of fw_window_rows.h>".  Bench lines and PMC
+ * fw_geometry.hip> win=<sha256 of fw_window_rows.h> ovl=<sha256 of the overlap sources>
+ * rsm=<sha256 of the resample sources> wb=<sha256 of fw_weights_bytes.h>".  Bench lines and PMC
  * profiles carry it, so a measurement names the code it measured. */
 const char* fw_build_info(void);
 
@@ -578,6 +579,81 @@ int fw_chains_read_overlap(fw_chains* c, int32_t what, void* dst, size_t bytes);
 int fw_chains_write_overlap(fw_chains* c, int32_t what, const void* src, size_t bytes);
 int fw_chains_overlap_reset(fw_chains* c);
 int fw_chains_overlap_info(const fw_chains* c, int64_t info[5]);
+
+/* ---- resampling plans across chains: clone, systematic resampling by cut ------------------
+ * The exchange step trades rungs, never plans; these two let a chain continue from another
+ * chain's plan, on the device and between launches, as the exchange, record, tally, geometry and
+ * overlap steps are placed; no run kernel changes.  They serve population annealing (a population
+ * at base 1, re-weighted and resampled while the base is stepped to the target), short bursts
+ * (restart every chain from the best plan) and seeding an ensemble from a few chains.  No
+ * reference counterpart: the reference runs one chain.
+ *
+ * fw_chains_clone_async: src int32 [n_chains]; chain i continues from the current plan of chain
+ * src[i].  Checked on the host before the device is touched, FW_EINVAL otherwise: every value in
+ * [0, n_chains), and every source a fixed point, src[src[i]] == src[i] (sources are then never
+ * written, so the gather works in place).  Enqueues on the handle's stream with no host
+ * synchronisation and without touching fw_chains_last_kernel_ms; src is copied to a device array
+ * the handle owns through a pinned staging slot (the host waits at most for the upload two calls
+ * back, never for the stream).
+ *   What moves from src[i] to i, the plan: the whole label record (the labels and the group sums
+ *   behind them), the k int64 populations, the stats fields cut, bnodes, npairs and stuck, under
+ *   FW_ACCEPT_BOUNDARY the k flagged-node counts, with sampled waits the current state's draw
+ *   (FW_READ_WAITS [i][1]), and family[i] (below).
+ *   What stays with i, the chain: attempts (its Philox counter), steps, accepts, every sum and
+ *   failure counter, yields, the wait sum, its thr row, its series, tallies, partners and
+ *   reference.  Clones diverge at once: chain i draws with its own global id and attempt counter.
+ * The result: after one or more runs a clone equals, bit for bit in everything a later run
+ * produces, the host route {read labels, stats (and waits); labels[i] = labels[src[i]], the four
+ * stats fields and the draw likewise; fw_chains_write}; before the first run it equals a handle
+ * created with the per-chain initial plans init[src[i]] (every chain yields its new initial plan
+ * once).  FW_ESTATE when the spatial maps are enabled (as fw_chains_write refuses plans under
+ * them), FW_EUNSUPPORTED on a laddered handle (fw_chains_set_ladder on a handle that has cloned
+ * is allowed).  One wave per destination chain with src[i] != i, 16-byte copies of the record,
+ * plain vector stores from one owner each, no atomics.
+ *
+ * fw_chains_resample_async: the map is drawn on the device, with no host synchronisation, by
+ * systematic resampling from integer weights of the cut, and applied as a clone.  q uint32
+ * [n_edges + 1] is non-increasing with q[0] == 2^30, sign is +1 or -1, 0 <= round < 2^32
+ * (FW_EINVAL otherwise); for a change of base b -> b', r = b'/b, the host passes q[d] =
+ * round(2^30 rho^d), rho = min(r, 1/r), sign = +1 if r > 1 else -1 (population.weight_table).
+ * C = n_chains <= 2^20 (FW_EUNSUPPORTED above); the refusals of clone apply.  Every quantity is
+ * an integer and no step depends on thread order:
+ *  1. cref = min (sign +1) or max (sign -1) of stats[i].cut over all chains (stuck chains like any
+ *     other); W_i = q[sign (cut_i - cref)]: the heaviest chain weighs 2^30, nothing underflows.
+ *  2. cum[i] = W_0 + .. + W_i (uint64), T = cum[C-1] <= 2^50, S2 = sum of (W_i >> 10)^2; the
+ *     effective sample size is (T >> 10)^2 / S2.
+ *  3. One Philox4x32-10 block, key = seed, ctr = (lo32(round), 2^30 | 2^29, lo32(chain_id0),
+ *     hi32(chain_id0)); u = x0.  Counter word 1 has bits 30 and 29 set and bit 31 clear: disjoint
+ *     from the proposal draws (word 1 < 2^30), the wait draws (bit 31 set) and the exchange
+ *     draws (2^30 | rung, rung < 64: bit 29 clear).
+ *  4. p_j = floor(((j 2^32 + u) T) / (C 2^32)), j = 0..C-1 (32-bit limbs: fw_resample_limbs.h).
+ *  5. The offspring count n_i = #{j : cum[i-1] <= p_j < cum[i]} (cum[-1] = 0); sum n_i = C and
+ *     floor(C W_i / T) <= n_i <= ceil(C W_i / T).
+ *  6. src[i] = i when n_i >= 1; the dead chains (n_i = 0) in ascending index receive the extra
+ *     copies (n_i - 1 per survivor) in ascending survivor index.  Every source is a fixed point.
+ *  7. The clone above with that map, read from the device array.
+ * The host counter n_resampled is incremented at enqueue.  Reads synchronise first:
+ * fw_chains_resample_info: info = {n_resampled, the last round (-1: none), T, S2, cref, survivors,
+ * max offspring (of the last resample), chains replaced by clones since creation (src[i] != i,
+ * over both entry points)}.  fw_chains_read_resample copies FW_RESAMPLE_SRC int32 [C] (the last
+ * map, from either entry point; FW_ESTATE before any), FW_RESAMPLE_FAMILY int32 [C] (the chain
+ * whose initial plan this plan descends from; family[i] = i at creation) or FW_RESAMPLE_WEIGHTS
+ * uint32 [C] (the last W; FW_ESTATE before a resample); FW_EINVAL for another kind or a buffer
+ * that is too small.  fw_chains_write_resample restores FW_RESAMPLE_FAMILY (checkpoints; every
+ * value in [0, C), else FW_EINVAL).  Left out: resampling across ranks, within the rungs of a
+ * ladder, under the spatial maps, weights from anything but the cut (the host can score between
+ * launches and call clone), adaptive bases, multinomial or residual schemes.  (These entry points
+ * arrived in 0.7 without a version bump; fw_build_info gained rsm=<sha256 of fw_resample.hip and
+ * fw_resample_limbs.h>.) */
+#define FW_RESAMPLE_SRC 0      /* int32  [n_chains] the last source map          */
+#define FW_RESAMPLE_FAMILY 1   /* int32  [n_chains] the ancestor chain of each plan */
+#define FW_RESAMPLE_WEIGHTS 2  /* uint32 [n_chains] the last resample's weights  */
+int fw_chains_clone_async(fw_chains* c, const int32_t* src /*[n_chains]*/);
+int fw_chains_resample_async(fw_chains* c, const uint32_t* q /*[n_edges+1]*/, int32_t sign,
+                             int64_t round);
+int fw_chains_resample_info(fw_chains* c, int64_t info[8]);
+int fw_chains_read_resample(fw_chains* c, int32_t what, void* dst, size_t bytes);
+int fw_chains_write_resample(fw_chains* c, int32_t what, const void* src, size_t bytes);
 
 /* Read a map (FW_MAP_*) of chains [chain0, chain0 + n_chains) as int64
  * [n_chains][len], or with FW_MAP_SUM its sum over those chains [len]; len is
