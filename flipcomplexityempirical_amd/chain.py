@@ -275,6 +275,7 @@ class Chains:
         # handle); _overlap_base as _tally_base
         self.partners = None
         self._overlap_base = 0
+        self._census_base = 0  # as _overlap_base, for the ensemble census
         # clone / resample: the round the next resample() takes by default, and the counts a
         # restored checkpoint started from (as _tally_base)
         self.resample_round = 0
@@ -411,7 +412,7 @@ class Chains:
     def run_tempered(self, steps_per_round: int, n_rounds: int, round0: Optional[int] = None,
                      max_retries: int = DEFAULT_MAX_RETRIES, record: bool = False,
                      tally: bool = False, geometry: bool = False,
-                     overlap: bool | str = False) -> None:
+                     overlap: bool | str = False, census: bool = False) -> None:
         """``n_rounds`` x (``steps_per_round`` steps, one exchange), enqueued back to back and
         waited for once.  Rounds are numbered from ``round0`` (default: where the last call
         stopped, ``ladder_round``), which fixes the parity and the draws of each exchange.
@@ -419,7 +420,8 @@ class Chains:
         its chain has just run on; with ``tally`` every round is run, tally, exchange, so a
         plan is counted under that rung too, and with ``geometry`` its districts are measured
         under it, and with ``overlap`` (True: against the reference, or "partner") its distance
-        is binned under it (run, tally, geometry, overlap, record, exchange)."""
+        is binned under it, and with ``census`` it enters the ensemble maps of that rung (run,
+        tally, geometry, overlap, census, record, exchange)."""
         if self.ladder_bases is None:
             raise ValueError("run_tempered needs a ladder (set_ladder)")
         r0 = self.ladder_round if round0 is None else int(round0)
@@ -432,6 +434,8 @@ class Chains:
                 self.geometry()
             if overlap:
                 self.overlap("reference" if overlap is True else overlap)
+            if census:
+                self.census()
             if record:
                 self.record()
             check(L.fw_chains_exchange_async(self._h, r0 + i))
@@ -519,11 +523,13 @@ class Chains:
 
     def run_sampled(self, steps_per_sample: int, n_samples: int,
                     max_retries: int = DEFAULT_MAX_RETRIES, tally: bool = False,
-                    geometry: bool = False, overlap: bool | str = False) -> None:
+                    geometry: bool = False, overlap: bool | str = False,
+                    census: bool = False) -> None:
         """``n_samples`` x (``steps_per_sample`` steps, one recorded sample), enqueued back to
         back and waited for once.  With ``tally`` every sample's plans are tallied as well, with
         ``geometry`` their districts are measured, with ``overlap`` (True: against the
-        reference, or "partner") they are compared (run, tally, geometry, overlap, record)."""
+        reference, or "partner") they are compared, with ``census`` they enter the ensemble maps
+        (run, tally, geometry, overlap, census, record)."""
         L = _lib.load()
         for _ in range(int(n_samples)):
             check(L.fw_chains_run_async(self._h, int(steps_per_sample), int(max_retries)))
@@ -533,6 +539,8 @@ class Chains:
                 self.geometry()
             if overlap:
                 self.overlap("reference" if overlap is True else overlap)
+            if census:
+                self.census()
             self.record()
         self.sync()
 
@@ -754,6 +762,64 @@ class Chains:
         check(_lib.load().fw_chains_overlap_reset(self._h))
         self._overlap_base = 0
 
+    # ------------------------------------------------------------- ensemble census
+    def enable_census(self, nodes: bool = True, edges: bool = True, boundary: bool = True) -> None:
+        """Keep maps over the graph summed across the chains (fw_chains_enable_census): node
+        occupancy per district (``nodes``), cut counts per edge (``edges``), boundary counts
+        per node (``boundary``); under a ladder one set per rung.  Zeroes the arrays and the
+        count; repeated, it replaces the previous set."""
+        what = ((_lib.CENSUS_NODES if nodes else 0) | (_lib.CENSUS_EDGES if edges else 0) |
+                (_lib.CENSUS_BOUNDARY if boundary else 0))
+        if not what:
+            raise ValueError("enable_census needs at least one of nodes, edges, boundary")
+        check(_lib.load().fw_chains_enable_census(self._h, what))
+        self._census_base = 0
+
+    def census(self) -> None:
+        """Add every chain's current plan to the enabled maps on the handle's stream, behind
+        the runs already there (fw_chains_census_async); no wait."""
+        check(_lib.load().fw_chains_census_async(self._h))
+
+    def census_info(self) -> dict:
+        info = np.zeros(5, np.int64)
+        check(_lib.load().fw_chains_census_info(self._h, ptr(info)))
+        what = int(info[0])
+        return {"nodes": bool(what & _lib.CENSUS_NODES), "edges": bool(what & _lib.CENSUS_EDGES),
+                "boundary": bool(what & _lib.CENSUS_BOUNDARY), "label_bits": int(info[1]),
+                "n_groups": int(info[2]), "n_edges": int(info[3]),
+                "n_measured": int(info[4]) + self._census_base}
+
+    def _read_census(self, what, *shape):
+        info = self.census_info()
+        arr = np.empty((info["n_groups"],) + tuple(info[s] if isinstance(s, str) else s
+                                                   for s in shape), np.uint64)
+        check(_lib.load().fw_chains_read_census(self._h, what, ptr(arr), arr.nbytes))
+        return arr
+
+    def node_occupancy(self) -> np.ndarray:
+        """uint64 [n_groups, n, k]: chains that labelled node v with district d, over all
+        censuses; one group, or one per rung under a ladder (``ensemble`` turns the arrays
+        into frequencies and maps)."""
+        return self._read_census(_lib.CENSUS_OCC, self.dgraph.n, self.k)
+
+    def edge_cut_counts(self) -> np.ndarray:
+        """uint64 [n_groups, n_edges]: chains that cut edge e (canonical ids: pairs u < w in
+        CSR row order), over all censuses."""
+        return self._read_census(_lib.CENSUS_ECUT, "n_edges")
+
+    def boundary_counts(self) -> np.ndarray:
+        """uint64 [n_groups, n]: chains in which node v had a neighbour of another district,
+        over all censuses."""
+        return self._read_census(_lib.CENSUS_BND, self.dgraph.n)
+
+    def census_counts(self) -> np.ndarray:
+        """uint64 [n_groups]: plans counted per group, over all censuses."""
+        return self._read_census(_lib.CENSUS_CNT)
+
+    def census_reset(self) -> None:
+        check(_lib.load().fw_chains_census_reset(self._h))
+        self._census_base = 0
+
     # ------------------------------------------------------------- resampling across chains
     def clone(self, src) -> None:
         """Chain i continues from the current plan of chain ``src[i]`` (fw_chains_clone_async):
@@ -809,11 +875,11 @@ class Chains:
     def run_annealed(self, bases, steps_per_stage: int, resample: bool = True,
                      record: bool = False, tally: bool = False, geometry: bool = False,
                      overlap: bool | str = False, max_retries: int = DEFAULT_MAX_RETRIES,
-                     estimate: bool = True):
+                     estimate: bool = True, census: bool = False):
         """Population annealing over ``bases``: at stage s every chain's bound table becomes
         that of ``bases[s]`` (a one-row ``set_schedule``, which stays in force afterwards), the
         population is resampled from ``bases[s - 1]`` (s >= 1, with ``resample``) and runs
-        ``steps_per_stage`` steps; then tally, geometry, overlap, record as asked.  The
+        ``steps_per_stage`` steps; then tally, geometry, overlap, census, record as asked.  The
         population is taken to sit at ``bases[0]`` on entry.  With ``estimate`` each stage's
         ``resample_info`` is read (one wait per stage) and the result is {"log_weight": the
         stages' ``population.log_weight_mean``, "log_z": their sum, "ess": the stages' effective
@@ -838,6 +904,8 @@ class Chains:
                 self.geometry()
             if overlap:
                 self.overlap("reference" if overlap is True else overlap)
+            if census:
+                self.census()
             if record:
                 self.record()
         self.sync()
@@ -953,6 +1021,17 @@ class Chains:
             ck["families"] = self.families()
             ck["n_resampled"], ck["n_clones"] = np.int64(rsm["n_resampled"]), np.int64(rsm["clones"])
             ck["resample_round"] = np.int64(self.resample_round)
+        cen = self.census_info()
+        if cen["nodes"] or cen["edges"] or cen["boundary"]:
+            ck["census_parts"] = np.array([cen["nodes"], cen["edges"], cen["boundary"]], bool)
+            ck["census_counts"] = self.census_counts()
+            if cen["nodes"]:
+                ck["census_occupancy"] = self.node_occupancy()
+            if cen["edges"]:
+                ck["census_edge_cut"] = self.edge_cut_counts()
+            if cen["boundary"]:
+                ck["census_boundary"] = self.boundary_counts()
+            ck["n_censuses"] = np.int64(cen["n_measured"])
         return ck
 
     def restore(self, ck: dict) -> None:
@@ -1077,6 +1156,17 @@ class Chains:
             self._resample_base += int(ck["n_resampled"]) - now["n_resampled"]
             self._clone_base += int(ck["n_clones"]) - now["clones"]
             self.resample_round = int(ck["resample_round"])
+        # the census after the ladder: its arrays are kept by rung
+        if "census_parts" in ck:
+            self.enable_census(*(bool(x) for x in np.asarray(ck["census_parts"])))
+            for what, key in ((_lib.CENSUS_CNT, "census_counts"),
+                              (_lib.CENSUS_OCC, "census_occupancy"),
+                              (_lib.CENSUS_ECUT, "census_edge_cut"),
+                              (_lib.CENSUS_BND, "census_boundary")):
+                if key in ck:
+                    a = np.ascontiguousarray(ck[key], np.uint64)
+                    check(L.fw_chains_write_census(self._h, what, ptr(a), a.nbytes))
+            self._census_base = int(ck["n_censuses"])  # enable_census zeroed the handle's count
 
     def save_checkpoint(self, path: str) -> None:
         ck = self.checkpoint()

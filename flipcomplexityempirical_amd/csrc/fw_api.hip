@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "fw_internal.h"
+#include "fw_census_plan.h"
 #include "fw_math.h"
 #include "fw_resample_limbs.h"
 
@@ -242,6 +243,13 @@ struct fw_chains {
   hipEvent_t rsm_ev[2] = {nullptr, nullptr};
   int rsm_slot = 0;
   std::vector<uint32_t> rsm_q;     // the table d_rsm_q holds (an equal table is not uploaded again)
+  // fw_chains_enable_census (cen.what == 0: off): the plan and, in FwCensusParams' names, the
+  // arrays derived from the graph; d_cen_acc uint64 [n_groups][cen.size], the group count in force
+  FwCensusParams cen{};
+  int64_t cen_measured = 0;
+  void* d_cen_graph[3] = {nullptr, nullptr, nullptr};  // tiles, ent, ebase
+  uint32_t* d_cen_part = nullptr;
+  uint64_t* d_cen_acc = nullptr;
 };
 
 namespace {
@@ -366,6 +374,201 @@ int ladder_snapshot(fw_chains* c, const fw_chain_stats* st) {
     sn[i] = FwRungSnap{st[i].yields, st[i].steps, st[i].accepts,
                        st[i].sum_cut, st[i].sum_bnodes, st[i].sum_invb};
   HIPCHK(hipMemcpy(c->d_snap, sn.data(), sizeof(FwRungSnap) * sn.size(), hipMemcpyHostToDevice));
+  return FW_OK;
+}
+
+// ---- the ensemble census (fw_chains_enable_census): plan and buffers of a handle with n_groups
+// groups, built aside so that on failure the handle keeps what it had
+struct CenBuild {
+  FwCensusParams p{};
+  void* graph[3] = {nullptr, nullptr, nullptr};
+  uint32_t* part = nullptr;
+  uint64_t* acc = nullptr;
+};
+
+void cen_free(CenBuild* b) {
+  void* bufs[] = {b->graph[0], b->graph[1], b->graph[2], b->part, b->acc};
+  for (void* x : bufs)
+    if (x) (void)hipFree(x);
+  *b = CenBuild{};
+}
+
+int cen_build(const fw_chains* c, int32_t what, int n_groups, CenBuild* out) {
+  const fw_graph* g = c->g;
+  const int n = g->n, lb = c->lb, k = c->k, E = g->nnz / 2;
+  const bool do_occ = what & FW_CENSUS_NODES, do_cut = what & FW_CENSUS_EDGES,
+             walk = what & (FW_CENSUS_EDGES | FW_CENSUS_BOUNDARY);
+  const int32_t* rowptr = g->rowptr.data();
+  const int32_t* col = g->col.data();
+  FwCensusParams p{};
+  p.n = n;
+  p.k = k;
+  p.lb = lb;
+  p.what = what;
+  p.lab_words = (int)(((int64_t)n * lb + 31) / 32);
+  p.n_groups = n_groups;
+  // the canonical id of a row's first upper edge: ids run over (u < w) in CSR row order
+  std::vector<int32_t> ebase((size_t)n + 1);
+  {
+    int e = 0;
+    for (int v = 0; v < n; ++v) {
+      ebase[v] = e;
+      for (int t = rowptr[v]; t < rowptr[v + 1]; ++t) e += col[t] > v;
+    }
+    ebase[n] = e;  // == E
+  }
+  // tiles: FW_CEN_TILE nodes; the longest tile when the rows of a short one already reach
+  // across most of a record (hub graphs, unordered node ids: every tile stages about the whole
+  // record, so fewer tiles read less); halved while the tile's counters and rows overflow LDS
+  const int env_tile = fw_census_env("FLIPWALK_CENSUS_TILE");
+  int T = env_tile >= 1 ? std::min(env_tile, FW_CEN_MAX_TILE) : FW_CEN_TILE;
+  bool fixed_tile = env_tile >= 1;
+  std::vector<int32_t> tiles;
+  int n_tiles = 0, nt = 64, wd_max = 0, fixed = 0;
+  for (;;) {
+    n_tiles = (n + T - 1) / T;
+    nt = (T + 63) / 64 * 64;
+    tiles.assign((size_t)n_tiles * FW_CEN_TILE_INTS, 0);
+    int max_ent = 0, max_edge = 0;
+    wd_max = 0;
+    for (int i = 0; i < n_tiles; ++i) {
+      const int t0 = i * T, t1 = std::min(n, t0 + T);
+      int lo, hi, wd0, wdn;
+      fw_cen_tile_reach(rowptr, col, t0, t1, &lo, &hi);
+      fw_cen_window(lo, hi, lb, &wd0, &wdn);
+      int32_t* td = &tiles[(size_t)i * FW_CEN_TILE_INTS];
+      td[0] = t0;
+      td[1] = t1 - t0;
+      td[2] = rowptr[t0];
+      td[3] = rowptr[t1] - rowptr[t0];
+      td[4] = ebase[t0];
+      td[5] = ebase[t1] - ebase[t0];
+      td[6] = wd0;
+      td[7] = wdn;
+      max_ent = std::max(max_ent, td[3]);
+      max_edge = std::max(max_edge, td[5]);
+      wd_max = std::max(wd_max, wdn);
+    }
+    p.off_ecut_lds = do_occ ? k * nt : 0;
+    p.off_ent_lds = p.off_ecut_lds + (do_cut ? max_edge : 0);
+    fixed = p.off_ent_lds + (walk ? max_ent : 0);
+    if (!fixed_tile && T < FW_CEN_MAX_TILE && n > T && 2 * wd_max > p.lab_words) {
+      T = FW_CEN_MAX_TILE;
+      fixed_tile = true;
+      continue;
+    }
+    if (fixed <= FW_CEN_LDS_WORDS || T == 1) break;  // one node: k 64 + 2 FW_MAX_DEG dwords
+    T = (T + 1) / 2;
+    fixed_tile = true;
+  }
+  // windows staged in LDS, as many chains at a time as the rest of 64 KB holds; none: the
+  // lanes read the records in HBM, and a tile's window is the record from its first dword
+  int batch = fw_census_env("FLIPWALK_CENSUS_STAGE") != 0 && wd_max > 0
+                  ? std::min(FW_CEN_MAX_BATCH, (FW_CEN_LDS_WORDS - fixed) / wd_max)
+                  : 0;
+  p.staged = batch >= 1;
+  if (!p.staged) {
+    batch = FW_CEN_MAX_BATCH;
+    wd_max = 0;
+    for (int i = 0; i < n_tiles; ++i) {
+      tiles[(size_t)i * FW_CEN_TILE_INTS + 6] = 0;
+      tiles[(size_t)i * FW_CEN_TILE_INTS + 7] = p.lab_words;
+    }
+  }
+  p.n_tiles = n_tiles;
+  p.nt = nt;
+  p.batch = batch;
+  p.wd_max = wd_max;
+  p.off_stage_lds = fixed;
+  p.lds_bytes = 4 * (fixed + batch * wd_max);
+  std::vector<uint32_t> ent((size_t)std::max(g->nnz, 1), 0u);
+  for (int i = 0; i < n_tiles; ++i) {
+    const int32_t* td = &tiles[(size_t)i * FW_CEN_TILE_INTS];
+    for (int v = td[0]; v < td[0] + td[1]; ++v)
+      for (int t = rowptr[v]; t < rowptr[v + 1]; ++t)
+        ent[t] = (uint32_t)((int64_t)col[t] * lb - (int64_t)td[6] * 32) << 1 | (col[t] > v ? 1u : 0u);
+  }
+  // a row of the partial sums and of the accumulators
+  int64_t off = 1;
+  p.off_occ = p.off_ecut = p.off_bnd = -1;
+  if (do_occ) p.off_occ = off, off += (int64_t)n * k;
+  if (do_cut) p.off_ecut = off, off += E;
+  if (what & FW_CENSUS_BOUNDARY) p.off_bnd = off, off += n;
+  p.size = off;
+  // slices: about 4096 workgroups, the partial sums within 64 MB (a group needs one slice at
+  // least).  The counters are 32 bits wide and a slice has at most n_chains < 2^31 members,
+  // so no counter bounds the slice length.
+  p.per_group = c->n_chains / n_groups;
+  const int env_slice = fw_census_env("FLIPWALK_CENSUS_SLICE");
+  if (env_slice >= 1) {
+    p.slice_len = std::min(env_slice, p.per_group);
+  } else {
+    int64_t spg = std::max<int64_t>(1, 4096 / ((int64_t)n_tiles * n_groups));
+    const int64_t cap = std::max<int64_t>(1, ((64ll << 20) / 4 / p.size) / n_groups);
+    spg = std::min(std::min(spg, cap), (int64_t)p.per_group);
+    p.slice_len = (int)((p.per_group + spg - 1) / spg);
+  }
+  p.spg = fw_cen_slices(p.per_group, p.slice_len);
+  if ((int64_t)n_tiles * n_groups * p.spg >= (1ll << 31))
+    return fail(FW_EUNSUPPORTED, "census: %d tiles x %d groups x %d slices", n_tiles, n_groups, p.spg);
+  CenBuild b;
+  const size_t sz[5] = {sizeof(int32_t) * tiles.size(), sizeof(uint32_t) * ent.size(),
+                        sizeof(int32_t) * ebase.size(),
+                        sizeof(uint32_t) * (size_t)n_groups * p.spg * (size_t)p.size,
+                        sizeof(uint64_t) * (size_t)n_groups * (size_t)p.size};
+  void* nb[5] = {};
+  bool ok = true;
+  for (int i = 0; i < 5 && ok; ++i) ok = hipMalloc(&nb[i], sz[i]) == hipSuccess;
+  b.graph[0] = nb[0];
+  b.graph[1] = nb[1];
+  b.graph[2] = nb[2];
+  b.part = static_cast<uint32_t*>(nb[3]);
+  b.acc = static_cast<uint64_t*>(nb[4]);
+  const bool up = ok && hipMemcpy(nb[0], tiles.data(), sz[0], hipMemcpyHostToDevice) == hipSuccess &&
+                  hipMemcpy(nb[1], ent.data(), sz[1], hipMemcpyHostToDevice) == hipSuccess &&
+                  hipMemcpy(nb[2], ebase.data(), sz[2], hipMemcpyHostToDevice) == hipSuccess &&
+                  hipMemset(nb[4], 0, sz[4]) == hipSuccess;
+  if (!up) {
+    cen_free(&b);
+    (void)hipGetLastError();
+    return ok ? fail(FW_EHIP, "census upload failed")
+              : fail(FW_ENOMEM, "census of %d chains in %d groups", c->n_chains, n_groups);
+  }
+  p.tiles = static_cast<const int32_t*>(nb[0]);
+  p.ent = static_cast<const uint32_t*>(nb[1]);
+  p.ebase = static_cast<const int32_t*>(nb[2]);
+  p.part = b.part;
+  b.p = p;
+  *out = b;
+  return FW_OK;
+}
+
+// the handle takes a finished build (its previous one is freed)
+void cen_adopt(fw_chains* c, const CenBuild& b) {
+  CenBuild old;
+  for (int i = 0; i < 3; ++i) old.graph[i] = c->d_cen_graph[i];
+  old.part = c->d_cen_part;
+  old.acc = c->d_cen_acc;
+  cen_free(&old);
+  for (int i = 0; i < 3; ++i) c->d_cen_graph[i] = b.graph[i];
+  c->d_cen_part = b.part;
+  c->d_cen_acc = b.acc;
+  c->cen = b.p;
+  c->cen_measured = 0;
+}
+
+// offset (uint64s into a row of the accumulators) and length of one array of the census
+int cen_array(const fw_chains* c, int32_t what, int64_t* off, int64_t* len) {
+  const FwCensusParams& p = c->cen;
+  switch (what) {
+    case FW_CENSUS_OCC: *off = p.off_occ, *len = (int64_t)p.n * p.k; break;
+    case FW_CENSUS_ECUT: *off = p.off_ecut, *len = c->g->nnz / 2; break;
+    case FW_CENSUS_BND: *off = p.off_bnd, *len = p.n; break;
+    case FW_CENSUS_CNT: *off = 0, *len = 1; break;
+    default: return fail(FW_EINVAL, "unknown census array %d", what);
+  }
+  if (!p.what) return fail(FW_ESTATE, "no census is enabled");
+  if (*off < 0) return fail(FW_ESTATE, "census array %d was not enabled (mask %d)", what, p.what);
   return FW_OK;
 }
 
@@ -568,7 +771,9 @@ void fw_chains_destroy(fw_chains* c) {
                   c->d_geo_w, c->d_geo_area, c->d_geo_ext, c->d_geo_out, c->d_geo_hist,
                   c->d_ovl_ref, c->d_ovl_partner, c->d_ovl_O, c->d_ovl_dist, c->d_ovl_hist,
                   c->d_rsm_src, c->d_rsm_family, c->d_rsm_q, c->d_rsm_w, c->d_rsm_cum, c->d_rsm_pts,
-                  c->d_rsm_lower, c->d_rsm_extra, c->d_rsm_info};
+                  c->d_rsm_lower, c->d_rsm_extra, c->d_rsm_info,
+                  c->d_cen_graph[0], c->d_cen_graph[1], c->d_cen_graph[2], c->d_cen_part,
+                  c->d_cen_acc};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   for (int i = 0; i < 2; ++i) {
@@ -1360,6 +1565,9 @@ int fw_chains_set_ladder(fw_chains* c, const double* thr_rows, const double* log
   // so is the plan-distance histogram
   unsigned long long* ovl_hist = nullptr;
   if (c->d_ovl_hist && ok) ok = hipMalloc(&ovl_hist, ovl_hist_bytes(c, n_rungs)) == hipSuccess;
+  // and the census arrays, whose slices are planned per group
+  CenBuild cen;
+  if (c->cen.what && ok && cen_build(c, c->cen.what, n_rungs, &cen) != FW_OK) ok = false;
   void* d_thr = shared ? nb[8] : (void*)c->d_thr;
   void* d_thr53 = shared ? nb[9] : (void*)c->d_thr53;
   const bool up =
@@ -1380,6 +1588,7 @@ int fw_chains_set_ladder(fw_chains* c, const double* thr_rows, const double* log
       if (b) (void)hipFree(b);
     if (geo_hist) (void)hipFree(geo_hist);
     if (ovl_hist) (void)hipFree(ovl_hist);
+    cen_free(&cen);
     return ok ? fail(FW_EHIP, "ladder upload failed")
               : fail(FW_ENOMEM, "ladder of %d rungs for %d chains", n_rungs, C);
   }
@@ -1404,6 +1613,7 @@ int fw_chains_set_ladder(fw_chains* c, const double* thr_rows, const double* log
     (void)hipFree(c->d_ovl_hist);
     c->d_ovl_hist = ovl_hist;
   }
+  if (cen.acc) cen_adopt(c, cen);
   c->d_thr = static_cast<double*>(d_thr);
   c->d_thr53 = static_cast<uint64_t*>(d_thr53);
   c->p.thr = c->d_thr;
@@ -2563,6 +2773,96 @@ int fw_chains_write_resample(fw_chains* c, int32_t what, const void* src, size_t
   if (const int rc = rsm_ensure(c)) return rc;
   HIPCHK(hipStreamSynchronize(c->stream));
   HIPCHK(hipMemcpy(c->d_rsm_family, src, need, hipMemcpyHostToDevice));
+  return FW_OK;
+}
+
+// ---------------------------------------------------------------- ensemble census
+int fw_chains_enable_census(fw_chains* c, int32_t what) {
+  const int32_t all = FW_CENSUS_NODES | FW_CENSUS_EDGES | FW_CENSUS_BOUNDARY;
+  if (what <= 0 || (what & ~all))
+    return fail(FW_EINVAL, "fw_chains_enable_census: mask %d is not a non-zero subset of %d", what, all);
+  if (!c) return fail(FW_EINVAL, "fw_chains_enable_census: null");
+  HIPCHK(hipSetDevice(c->g->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  CenBuild b;
+  if (const int rc = cen_build(c, what, c->n_rungs ? c->n_rungs : 1, &b)) return rc;
+  cen_adopt(c, b);
+  return FW_OK;
+}
+
+int fw_chains_census_async(fw_chains* c) {
+  if (!c) return fail(FW_EINVAL, "null handle");
+  if (!c->cen.what) return fail(FW_ESTATE, "fw_chains_census_async: no census is enabled");
+  HIPCHK(hipSetDevice(c->g->device));
+  FwCensusParams p = c->cen;
+  p.labels = c->d_labels;
+  p.lab_stride = c->p.lab_stride;
+  p.rowptr = c->g->d_rowptr;
+  p.chain_of = c->n_rungs ? c->d_chain_of : nullptr;
+  // like the exchange, record and tally steps: the run timing events are left alone
+  int le = fw_launch_census(p, c->stream);
+  if (le != 0)
+    return fail(FW_EHIP, "census launch failed: %s", hipGetErrorString((hipError_t)le));
+  FwCensusAddParams a{};
+  a.part = c->d_cen_part;
+  a.acc = c->d_cen_acc;
+  a.size = p.size;
+  a.n_groups = p.n_groups;
+  a.spg = p.spg;
+  le = fw_launch_census_add(a, c->stream);
+  if (le != 0)
+    return fail(FW_EHIP, "census sum launch failed: %s", hipGetErrorString((hipError_t)le));
+  c->cen_measured += 1;
+  return FW_OK;
+}
+
+int fw_chains_read_census(fw_chains* c, int32_t what, void* dst, size_t bytes) {
+  if (!c) return fail(FW_EINVAL, "fw_chains_read_census: null");
+  int64_t off = 0, len = 0;
+  if (const int rc = cen_array(c, what, &off, &len)) return rc;
+  const size_t row = sizeof(uint64_t) * (size_t)len, need = row * (size_t)c->cen.n_groups;
+  if (bytes < need || !dst) return fail(FW_EINVAL, "the census array needs %zu bytes", need);
+  HIPCHK(hipSetDevice(c->g->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (row)
+    HIPCHK(hipMemcpy2D(dst, row, c->d_cen_acc + off, sizeof(uint64_t) * (size_t)c->cen.size, row,
+                       (size_t)c->cen.n_groups, hipMemcpyDeviceToHost));
+  return FW_OK;
+}
+
+int fw_chains_write_census(fw_chains* c, int32_t what, const void* src, size_t bytes) {
+  if (!c) return fail(FW_EINVAL, "fw_chains_write_census: null");
+  int64_t off = 0, len = 0;
+  if (const int rc = cen_array(c, what, &off, &len)) return rc;
+  const size_t row = sizeof(uint64_t) * (size_t)len, need = row * (size_t)c->cen.n_groups;
+  if (bytes < need || !src) return fail(FW_EINVAL, "the census array needs %zu bytes", need);
+  HIPCHK(hipSetDevice(c->g->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (row)
+    HIPCHK(hipMemcpy2D(c->d_cen_acc + off, sizeof(uint64_t) * (size_t)c->cen.size, src, row, row,
+                       (size_t)c->cen.n_groups, hipMemcpyHostToDevice));
+  return FW_OK;
+}
+
+int fw_chains_census_reset(fw_chains* c) {
+  if (!c) return fail(FW_EINVAL, "null handle");
+  if (c->d_cen_acc) {
+    HIPCHK(hipSetDevice(c->g->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemset(c->d_cen_acc, 0,
+                     sizeof(uint64_t) * (size_t)c->cen.n_groups * (size_t)c->cen.size));
+  }
+  c->cen_measured = 0;
+  return FW_OK;
+}
+
+int fw_chains_census_info(const fw_chains* c, int64_t info[5]) {
+  if (!c || !info) return fail(FW_EINVAL, "fw_chains_census_info: null");
+  info[0] = c->cen.what;
+  info[1] = c->lb;
+  info[2] = c->n_rungs ? c->n_rungs : 1;
+  info[3] = c->g->nnz / 2;
+  info[4] = c->cen_measured;
   return FW_OK;
 }
 

@@ -362,6 +362,51 @@ struct FwResampleParams {
   int64_t chain_id0;
 };
 
+// ---- ensemble census: maps over the graph, summed across chains (fw_census.hip) -------------
+#define FW_CEN_TILE 256          // nodes of a tile by default (one lane each)
+#define FW_CEN_MAX_TILE 1024     // and at the most: a workgroup's threads
+#define FW_CEN_MAX_BATCH 16      // chains staged in LDS between two barriers at the most
+#define FW_CEN_LDS_WORDS 16384   // dwords of LDS a workgroup may plan with (64 KB)
+#define FW_CEN_TILE_INTS 8       // int32 per tile record
+
+// fw_chains_census_async, first stage.  Workgroup (tile, slice) counts, over the chains of its
+// slice, the nodes, upper edges and boundary flags of its tile and stores them as uint32 into
+// row `slice` of part.  A tile record is {node0, nodes, entry0 (rowptr[node0]), entries, edge0
+// (first canonical edge id with its lower endpoint in the tile), edges, wd0, wdn (the dwords
+// [wd0, wd0 + wdn) of a record its nodes and their neighbours lie in; staged == 0: 0 and the
+// record's label words)}.  ent[t] of CSR entry t = (v, w): (w lb - 32 wd0(tile of v)) << 1 |
+// (w > v).  Slice sl = g spg + s holds the members [s slice_len, ..) of group g; member i of
+// group g is chain chain_of[i n_groups + g] under a ladder, else chain i.
+struct FwCensusParams {
+  const uint8_t* labels;    // packed lb-bit label records, chain c at labels + c * lab_stride
+  int64_t lab_stride;       // bytes, a multiple of 16
+  const int32_t* rowptr;    // [n + 1]
+  const int32_t* tiles;     // [n_tiles][FW_CEN_TILE_INTS]
+  const uint32_t* ent;      // [nnz]
+  const int32_t* ebase;     // [n] canonical id of the first edge (v, w > v) of row v
+  const int32_t* chain_of;  // [per_group][n_groups] or null (no ladder)
+  uint32_t* part;           // [n_groups * spg][size]
+  int32_t n, k, lb, what, lab_words;
+  int32_t n_tiles, n_groups, spg, slice_len, per_group;
+  int32_t nt, staged, batch, wd_max;        // threads; the LDS staging of label windows
+  int32_t off_ecut_lds, off_ent_lds, off_stage_lds, lds_bytes;  // dwords, dwords, dwords, bytes
+  // a row of part and of the accumulators: cnt at 0, then the enabled parts (-1: absent)
+  int64_t size, off_occ, off_ecut, off_bnd;
+};
+
+// second stage: acc[g][j] += sum over the slices s of group g of part[g spg + s][j]
+struct FwCensusAddParams {
+  const uint32_t* part;
+  uint64_t* acc;  // [n_groups][size]
+  int64_t size;
+  int32_t n_groups, spg;
+};
+
+// Host-side launchers implemented in fw_census.hip.
+int fw_census_env(const char* name);  // a test knob's value, -1 when unset
+int fw_launch_census(const FwCensusParams& p, void* stream);
+int fw_launch_census_add(const FwCensusAddParams& a, void* stream);
+
 // Host-side launchers implemented in fw_resample.hip.
 int fw_launch_clone(const FwCloneParams& p, void* stream);
 int fw_launch_resample_map(const FwResampleParams& p, void* stream);

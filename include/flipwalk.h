@@ -655,6 +655,72 @@ int fw_chains_resample_info(fw_chains* c, int64_t info[8]);
 int fw_chains_read_resample(fw_chains* c, int32_t what, void* dst, size_t bytes);
 int fw_chains_write_resample(fw_chains* c, int32_t what, const void* src, size_t bytes);
 
+/* ---- ensemble census: node occupancy, edge cut and boundary counts across the chains -------
+ * The reference's heat maps (cut_times per edge, part_sum per node, the boundary frequencies)
+ * are sums over the steps of one chain; fw_chains_enable_maps reproduces them per chain, inside
+ * the run kernels.  With many chains the map a user wants is the one across the ensemble at a
+ * sampled instant: how often node v lies in district d, how often edge e is cut, how often v
+ * lies on a boundary; under a ladder, per rung.  Every other measurement reduces over the nodes
+ * of one chain; a census fixes a node or an edge and sums over the chains.  It runs on the
+ * device and between launches, as the exchange, record, tally, geometry and overlap steps are
+ * placed, from the label records; no run kernel changes, and it only reads plans: it works on
+ * every label width, on both run kernels' records, with the spatial maps enabled and on cloned
+ * or resampled populations.
+ *
+ * fw_chains_enable_census: what is a non-zero mask of FW_CENSUS_NODES, FW_CENSUS_EDGES and
+ * FW_CENSUS_BOUNDARY (FW_EINVAL for any other value, checked before the handle is looked at).
+ * Allocates and zeroes the accumulators and zeroes n_measured; repeated, it replaces the
+ * previous set (FW_ENOMEM when the arrays cannot be allocated: the handle keeps what it had).
+ * What the passes need from the graph is derived here, once: node tiles with their CSR rows and
+ * canonical edge ranges, the range of label words each tile's rows reach, and the slices.
+ *
+ * fw_chains_census_async (FW_ESTATE before fw_chains_enable_census) enqueues on the handle's
+ * stream, with no host synchronisation and without touching fw_chains_last_kernel_ms.  With X_c
+ * the current plan of chain c (stuck chains like any other), g(c) the chain's current rung under
+ * a ladder, else 0 (read on the device from the exchange step's own arrays: the host does not
+ * wait for them), and e = (u, w) the canonical edge id (pairs u < w in CSR row order, as the
+ * geometry uses), it adds
+ *   cnt[g]       += #{c : g(c) = g}
+ *   occ[g][v][d] += #{c : g(c) = g and X_c(v) = d}                                  (NODES)
+ *   ecut[g][e]   += #{c : g(c) = g and X_c(u) != X_c(w)}                            (EDGES)
+ *   bnd[g][v]    += #{c : g(c) = g and some neighbour w of v has X_c(w) != X_c(v)}  (BOUNDARY)
+ * The host counter n_measured is incremented at enqueue.  All sums are integers.  A first
+ * kernel counts, per node tile and per slice of a group's chains, into 32-bit counters with one
+ * owner each and leaves them with plain vector stores in a [slice][..] buffer; a second adds
+ * the slices, in ascending order, into the uint64 accumulators, one owner each: no atomics in
+ * HBM, and no dependence on thread order, tile sizes or slice sizes.  A slice has fewer than
+ * 2^31 chains (n_chains is an int32), so the 32-bit counters bound no slice length.
+ *
+ * fw_chains_read_census synchronises, then copies one array, accumulated over all measurements
+ * (n_groups = n_rungs, or 1 without a ladder):
+ *   FW_CENSUS_OCC   uint64 [n_groups][n][k]
+ *   FW_CENSUS_ECUT  uint64 [n_groups][n_edges]
+ *   FW_CENSUS_BND   uint64 [n_groups][n]
+ *   FW_CENSUS_CNT   uint64 [n_groups]
+ * FW_ESTATE when the part was not enabled (CNT comes with any part), FW_EINVAL for another kind
+ * or a buffer that is too small.  fw_chains_write_census restores any of the four (checkpoints;
+ * n_measured is not changed); fw_chains_census_reset zeroes the arrays and n_measured.
+ * fw_chains_census_info: info = {the enabled mask (0: none), label bits per node of the
+ * handle's plans, n_groups, n_edges, n_measured}.  fw_chains_reset_observables leaves all of
+ * this alone; fw_chains_set_ladder re-sizes the arrays for the new group count and zeroes them
+ * and n_measured.  Left out: merging across ranks (the arrays are plain sums a caller can
+ * all-reduce), weights per node or per chain, node-pair co-assignment.  (These entry points
+ * arrived in 0.7 without a version bump; fw_build_info gained cen=<sha256 of fw_census.hip and
+ * fw_census_plan.h>.) */
+#define FW_CENSUS_NODES    1   /* enable mask: occupancy per node and district */
+#define FW_CENSUS_EDGES    2   /* enable mask: cut count per edge              */
+#define FW_CENSUS_BOUNDARY 4   /* enable mask: boundary count per node         */
+#define FW_CENSUS_OCC  1       /* uint64 [n_groups][n][k]     */
+#define FW_CENSUS_ECUT 2       /* uint64 [n_groups][n_edges]  */
+#define FW_CENSUS_BND  4       /* uint64 [n_groups][n]        */
+#define FW_CENSUS_CNT  8       /* uint64 [n_groups]           */
+int fw_chains_enable_census(fw_chains* c, int32_t what);
+int fw_chains_census_async(fw_chains* c);
+int fw_chains_read_census(fw_chains* c, int32_t what, void* dst, size_t bytes);
+int fw_chains_write_census(fw_chains* c, int32_t what, const void* src, size_t bytes);
+int fw_chains_census_reset(fw_chains* c);
+int fw_chains_census_info(const fw_chains* c, int64_t info[5]);
+
 /* Read a map (FW_MAP_*) of chains [chain0, chain0 + n_chains) as int64
  * [n_chains][len], or with FW_MAP_SUM its sum over those chains [len]; len is
  * n_edges for FW_MAP_CUT_TIMES and n otherwise.  Values are current through the
