@@ -276,6 +276,7 @@ class Chains:
         self.partners = None
         self._overlap_base = 0
         self._census_base = 0  # as _overlap_base, for the ensemble census
+        self._pairdist_base = 0  # and for the pairwise plan distances
         # clone / resample: the round the next resample() takes by default, and the counts a
         # restored checkpoint started from (as _tally_base)
         self.resample_round = 0
@@ -524,12 +525,13 @@ class Chains:
     def run_sampled(self, steps_per_sample: int, n_samples: int,
                     max_retries: int = DEFAULT_MAX_RETRIES, tally: bool = False,
                     geometry: bool = False, overlap: bool | str = False,
-                    census: bool = False) -> None:
+                    census: bool = False, pairs=False) -> None:
         """``n_samples`` x (``steps_per_sample`` steps, one recorded sample), enqueued back to
         back and waited for once.  With ``tally`` every sample's plans are tallied as well, with
         ``geometry`` their districts are measured, with ``overlap`` (True: against the
-        reference, or "partner") they are compared, with ``census`` they enter the ensemble maps
-        (run, tally, geometry, overlap, census, record)."""
+        reference, or "partner") they are compared, with ``census`` they enter the ensemble maps,
+        with ``pairs`` (True: all chains, or a member list) their pairwise distances are measured
+        (run, tally, geometry, overlap, census, pairs, record)."""
         L = _lib.load()
         for _ in range(int(n_samples)):
             check(L.fw_chains_run_async(self._h, int(steps_per_sample), int(max_retries)))
@@ -541,6 +543,8 @@ class Chains:
                 self.overlap("reference" if overlap is True else overlap)
             if census:
                 self.census()
+            if pairs is not False and pairs is not None:
+                self.pair_distances(None if pairs is True else pairs)
             self.record()
         self.sync()
 
@@ -820,6 +824,67 @@ class Chains:
         check(_lib.load().fw_chains_census_reset(self._h))
         self._census_base = 0
 
+    # ------------------------------------------------------------- pairwise plan distances
+    def pair_distances(self, a=None, b=None) -> None:
+        """Measure the Hamming distances between the current plans of the chains ``a`` and the
+        chains ``b`` (member lists of chain ids, duplicates allowed; ``a=None``: all chains;
+        ``b=None``: ``b = a``, the symmetric case) on the handle's stream, behind the runs
+        already there (fw_chains_pairdist_async); no wait.  ``distance_matrix``,
+        ``distance_rowsums`` and ``nearest_plans`` read the last measurement,
+        ``pair_distance_hist`` the histogram over all of them."""
+        if a is None:
+            if b is None and self.n_chains ** 2 > _lib.PAIRDIST_MAX_PAIRS:
+                raise ValueError(f"{self.n_chains} chains give more than 2^28 pairs: "
+                                 "pass a member list")
+            a = np.arange(self.n_chains, dtype=np.int32)
+        a = np.ascontiguousarray(np.asarray(a).ravel(), np.int32)
+        if b is None:
+            check(_lib.load().fw_chains_pairdist_async(self._h, ptr(a), a.size, None, 0))
+            return
+        b = np.ascontiguousarray(np.asarray(b).ravel(), np.int32)
+        if b.size < 1:
+            raise ValueError("pair_distances: b is empty")
+        check(_lib.load().fw_chains_pairdist_async(self._h, ptr(a), a.size, ptr(b), b.size))
+
+    def pair_distance_info(self) -> dict:
+        info = np.zeros(7, np.int64)
+        check(_lib.load().fw_chains_pairdist_info(self._h, ptr(info)))
+        return {"ma": int(info[0]), "mb": int(info[1]), "symmetric": bool(info[2]),
+                "label_bits": int(info[3]), "n_measured": int(info[4]) + self._pairdist_base,
+                "tile": int(info[5]), "chunk": int(info[6])}
+
+    def _read_pairdist(self, what, arr):
+        check(_lib.load().fw_chains_read_pairdist(self._h, what, ptr(arr), arr.nbytes))
+        return arr
+
+    def distance_matrix(self) -> np.ndarray:
+        """int32 [ma, mb]: D[i, j] = nodes at which the plans of chains a[i] and b[j] differ
+        (districts by name), as of the last ``pair_distances``."""
+        info = self.pair_distance_info()
+        return self._read_pairdist(_lib.PAIRDIST_MATRIX,
+                                   np.empty((max(info["ma"], 1), max(info["mb"], 1)), np.int32))
+
+    def distance_rowsums(self) -> np.ndarray:
+        """int64 [ma]: the row sums of ``distance_matrix()`` (``plancloud.medoid``)."""
+        info = self.pair_distance_info()
+        return self._read_pairdist(_lib.PAIRDIST_ROWSUM, np.empty(max(info["ma"], 1), np.int64))
+
+    def nearest_plans(self) -> np.ndarray:
+        """int32 [ma, 2]: per row the least distance and the lowest position j attaining it; in
+        the symmetric case position i itself is left out ((-1, -1) for a single member)."""
+        info = self.pair_distance_info()
+        return self._read_pairdist(_lib.PAIRDIST_NEAREST,
+                                   np.empty((max(info["ma"], 1), 2), np.int32))
+
+    def pair_distance_hist(self) -> np.ndarray:
+        """uint64 [n + 1]: counts of the measured distances over all ``pair_distances`` since
+        the last reset: positions i < j in the symmetric case, every (i, j) otherwise."""
+        return self._read_pairdist(_lib.PAIRDIST_HIST, np.empty(self.dgraph.n + 1, np.uint64))
+
+    def pair_distance_reset(self) -> None:
+        check(_lib.load().fw_chains_pairdist_reset(self._h))
+        self._pairdist_base = 0
+
     # ------------------------------------------------------------- resampling across chains
     def clone(self, src) -> None:
         """Chain i continues from the current plan of chain ``src[i]`` (fw_chains_clone_async):
@@ -875,11 +940,12 @@ class Chains:
     def run_annealed(self, bases, steps_per_stage: int, resample: bool = True,
                      record: bool = False, tally: bool = False, geometry: bool = False,
                      overlap: bool | str = False, max_retries: int = DEFAULT_MAX_RETRIES,
-                     estimate: bool = True, census: bool = False):
+                     estimate: bool = True, census: bool = False, pairs=False):
         """Population annealing over ``bases``: at stage s every chain's bound table becomes
         that of ``bases[s]`` (a one-row ``set_schedule``, which stays in force afterwards), the
         population is resampled from ``bases[s - 1]`` (s >= 1, with ``resample``) and runs
-        ``steps_per_stage`` steps; then tally, geometry, overlap, census, record as asked.  The
+        ``steps_per_stage`` steps; then tally, geometry, overlap, census, pairs (True: all chains,
+        or a member list: one symmetric ``pair_distances``), record as asked.  The
         population is taken to sit at ``bases[0]`` on entry.  With ``estimate`` each stage's
         ``resample_info`` is read (one wait per stage) and the result is {"log_weight": the
         stages' ``population.log_weight_mean``, "log_z": their sum, "ess": the stages' effective
@@ -906,6 +972,8 @@ class Chains:
                 self.overlap("reference" if overlap is True else overlap)
             if census:
                 self.census()
+            if pairs is not False and pairs is not None:
+                self.pair_distances(None if pairs is True else pairs)
             if record:
                 self.record()
         self.sync()
@@ -1032,6 +1100,10 @@ class Chains:
             if cen["boundary"]:
                 ck["census_boundary"] = self.boundary_counts()
             ck["n_censuses"] = np.int64(cen["n_measured"])
+        pwd = self.pair_distance_info()
+        if pwd["n_measured"]:
+            ck["pair_distance_hist"] = self.pair_distance_hist()
+            ck["n_pair_distances"] = np.int64(pwd["n_measured"])
         return ck
 
     def restore(self, ck: dict) -> None:
@@ -1167,6 +1239,14 @@ class Chains:
                     a = np.ascontiguousarray(ck[key], np.uint64)
                     check(L.fw_chains_write_census(self._h, what, ptr(a), a.nbytes))
             self._census_base = int(ck["n_censuses"])  # enable_census zeroed the handle's count
+        if "pair_distance_hist" in ck:
+            hist = np.ascontiguousarray(ck["pair_distance_hist"], np.uint64)
+            if hist.shape != (self.dgraph.n + 1,):
+                raise ValueError(f"pair_distance_hist has shape {hist.shape}, the handle's is "
+                                 f"{(self.dgraph.n + 1,)}")
+            check(L.fw_chains_write_pairdist(self._h, _lib.PAIRDIST_HIST, ptr(hist), hist.nbytes))
+            self._pairdist_base = int(ck["n_pair_distances"]) - (
+                self.pair_distance_info()["n_measured"] - self._pairdist_base)
 
     def save_checkpoint(self, path: str) -> None:
         ck = self.checkpoint()

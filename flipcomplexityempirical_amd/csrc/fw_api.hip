@@ -17,6 +17,7 @@
 #include "fw_internal.h"
 #include "fw_census_plan.h"
 #include "fw_math.h"
+#include "fw_pairdist_plan.h"
 #include "fw_resample_limbs.h"
 
 namespace {
@@ -250,6 +251,24 @@ struct fw_chains {
   void* d_cen_graph[3] = {nullptr, nullptr, nullptr};  // tiles, ent, ebase
   uint32_t* d_cen_part = nullptr;
   uint64_t* d_cen_acc = nullptr;
+  // fw_chains_pairdist_async (pwd_have false: nothing measured yet); FwPairdistParams names the
+  // arrays.  Buffers grow with the lists and are never shrunk; d_pwd_hist uint64 [n + 1]
+  bool pwd_have = false, pwd_sym = false;
+  int32_t pwd_ma = 0, pwd_mb = 0, pwd_tile = 0, pwd_chunk = 0;
+  int64_t pwd_measured = 0;
+  int32_t* d_pwd_list[2] = {nullptr, nullptr};
+  size_t pwd_list_cap[2] = {0, 0};   // elements
+  int32_t* d_pwd_D = nullptr;
+  size_t pwd_D_cap = 0;              // elements
+  int64_t* d_pwd_rowsum = nullptr;
+  int32_t* d_pwd_near = nullptr;
+  size_t pwd_row_cap = 0;            // rows
+  unsigned long long* d_pwd_hist = nullptr;
+  // the lists' uploads: two pinned slots, each with the event of its last copy (as rsm_stage)
+  void* pwd_stage[2] = {nullptr, nullptr};
+  size_t pwd_stage_cap[2] = {0, 0};  // bytes
+  hipEvent_t pwd_ev[2] = {nullptr, nullptr};
+  int pwd_slot = 0;
 };
 
 namespace {
@@ -773,9 +792,14 @@ void fw_chains_destroy(fw_chains* c) {
                   c->d_rsm_src, c->d_rsm_family, c->d_rsm_q, c->d_rsm_w, c->d_rsm_cum, c->d_rsm_pts,
                   c->d_rsm_lower, c->d_rsm_extra, c->d_rsm_info,
                   c->d_cen_graph[0], c->d_cen_graph[1], c->d_cen_graph[2], c->d_cen_part,
-                  c->d_cen_acc};
+                  c->d_cen_acc, c->d_pwd_list[0], c->d_pwd_list[1], c->d_pwd_D, c->d_pwd_rowsum,
+                  c->d_pwd_near, c->d_pwd_hist};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
+  for (int i = 0; i < 2; ++i) {
+    if (c->pwd_stage[i]) (void)hipHostFree(c->pwd_stage[i]);
+    if (c->pwd_ev[i]) (void)hipEventDestroy(c->pwd_ev[i]);
+  }
   for (int i = 0; i < 2; ++i) {
     if (c->rsm_stage[i]) (void)hipHostFree(c->rsm_stage[i]);
     if (c->rsm_ev[i]) (void)hipEventDestroy(c->rsm_ev[i]);
@@ -2863,6 +2887,241 @@ int fw_chains_census_info(const fw_chains* c, int64_t info[5]) {
   info[2] = c->n_rungs ? c->n_rungs : 1;
   info[3] = c->g->nnz / 2;
   info[4] = c->cen_measured;
+  return FW_OK;
+}
+
+// ---------------------------------------------------------------- pairwise plan distances
+namespace {
+
+size_t pwd_hist_bytes(const fw_chains* c) {
+  return sizeof(unsigned long long) * ((size_t)c->g->n + 1);
+}
+
+int pwd_ensure_hist(fw_chains* c) {
+  if (c->d_pwd_hist) return FW_OK;
+  void* h = nullptr;
+  if (hipMalloc(&h, pwd_hist_bytes(c)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(FW_ENOMEM, "pair-distance histogram of %d bins", c->g->n + 1);
+  }
+  if (hipMemset(h, 0, pwd_hist_bytes(c)) != hipSuccess) {
+    (void)hipFree(h);
+    return fail(FW_EHIP, "the pair-distance histogram could not be zeroed");
+  }
+  c->d_pwd_hist = static_cast<unsigned long long*>(h);
+  return FW_OK;
+}
+
+// *buf holds at least `want` bytes afterwards.  The new buffer is allocated before the old one
+// is let go, so on failure the handle keeps what it had; a kernel in flight may still use the
+// old one, so the stream is waited for before it is freed (only when a buffer grows).
+int pwd_grow(fw_chains* c, void** buf, size_t* cap, size_t want, size_t unit, const char* what) {
+  if (*cap >= want) return FW_OK;
+  void* nb = nullptr;
+  if (hipMalloc(&nb, want * unit) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(FW_ENOMEM, "pair distances: %s of %zu elements", what, want);
+  }
+  if (*buf) {
+    if (hipStreamSynchronize(c->stream) != hipSuccess) {
+      (void)hipFree(nb);
+      return fail(FW_EHIP, "pair distances: the stream could not be waited for");
+    }
+    (void)hipFree(*buf);
+  }
+  *buf = nb;
+  *cap = want;
+  return FW_OK;
+}
+
+// a list -> the device on the handle's stream through a pinned slot: the host waits only for
+// the copy that last used the slot, never for the stream
+int pwd_upload(fw_chains* c, int32_t* dst, const int32_t* src, int32_t m) {
+  const int s = c->pwd_slot;
+  const size_t bytes = sizeof(int32_t) * (size_t)m;
+  if (!c->pwd_ev[s] &&
+      hipEventCreateWithFlags(&c->pwd_ev[s], hipEventDisableTiming) != hipSuccess) {
+    c->pwd_ev[s] = nullptr;
+    (void)hipGetLastError();
+    return fail(FW_ENOMEM, "pair distances: no event for a staging slot");
+  }
+  HIPCHK(hipEventSynchronize(c->pwd_ev[s]));
+  if (c->pwd_stage_cap[s] < bytes) {
+    void* ns = nullptr;
+    if (hipHostMalloc(&ns, bytes, hipHostMallocDefault) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(FW_ENOMEM, "pair distances: a pinned slot of %zu bytes", bytes);
+    }
+    if (c->pwd_stage[s]) (void)hipHostFree(c->pwd_stage[s]);
+    c->pwd_stage[s] = ns;
+    c->pwd_stage_cap[s] = bytes;
+  }
+  c->pwd_slot ^= 1;
+  std::memcpy(c->pwd_stage[s], src, bytes);
+  HIPCHK(hipMemcpyAsync(dst, c->pwd_stage[s], bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipEventRecord(c->pwd_ev[s], c->stream));
+  return FW_OK;
+}
+
+int pwd_bytes(const fw_chains* c, int32_t what, size_t* need) {
+  switch (what) {
+    case FW_PAIRDIST_MATRIX: *need = sizeof(int32_t) * (size_t)c->pwd_ma * (size_t)c->pwd_mb; return FW_OK;
+    case FW_PAIRDIST_ROWSUM: *need = sizeof(int64_t) * (size_t)c->pwd_ma; return FW_OK;
+    case FW_PAIRDIST_NEAREST: *need = sizeof(int32_t) * 2 * (size_t)c->pwd_ma; return FW_OK;
+    case FW_PAIRDIST_HIST: *need = pwd_hist_bytes(c); return FW_OK;
+    default: return fail(FW_EINVAL, "unknown pair-distance kind %d", what);
+  }
+}
+
+}  // namespace
+
+int fw_chains_pairdist_async(fw_chains* c, const int32_t* a, int32_t ma, const int32_t* b,
+                             int32_t mb) {
+  if (!c) return fail(FW_EINVAL, "fw_chains_pairdist_async: null handle");
+  if (!a) return fail(FW_EINVAL, "fw_chains_pairdist_async: null list a");
+  if (ma < 1) return fail(FW_EINVAL, "fw_chains_pairdist_async: ma = %d < 1", ma);
+  if (b && mb < 1) return fail(FW_EINVAL, "fw_chains_pairdist_async: mb = %d < 1", mb);
+  const bool sym = !b;
+  if (sym) mb = ma;
+  for (int i = 0; i < ma; ++i)
+    if (a[i] < 0 || a[i] >= c->n_chains)
+      return fail(FW_EINVAL, "a[%d] = %d outside [0, %d)", i, a[i], c->n_chains);
+  for (int j = 0; b && j < mb; ++j)
+    if (b[j] < 0 || b[j] >= c->n_chains)
+      return fail(FW_EINVAL, "b[%d] = %d outside [0, %d)", j, b[j], c->n_chains);
+  if ((int64_t)ma * mb > FW_PWD_MAX_PAIRS)
+    return fail(FW_EUNSUPPORTED, "%d x %d pairs > 2^28", ma, mb);
+  HIPCHK(hipSetDevice(c->g->device));
+  if (const int rc = pwd_ensure_hist(c)) return rc;
+  if (const int rc = pwd_grow(c, (void**)&c->d_pwd_list[0], &c->pwd_list_cap[0], (size_t)ma,
+                              sizeof(int32_t), "list a"))
+    return rc;
+  if (!sym)
+    if (const int rc = pwd_grow(c, (void**)&c->d_pwd_list[1], &c->pwd_list_cap[1], (size_t)mb,
+                                sizeof(int32_t), "list b"))
+      return rc;
+  if (const int rc = pwd_grow(c, (void**)&c->d_pwd_D, &c->pwd_D_cap, (size_t)ma * (size_t)mb,
+                              sizeof(int32_t), "matrix"))
+    return rc;
+  if (c->pwd_row_cap < (size_t)ma) {
+    // both row arrays or neither: the second is grown first under its own count
+    size_t cap_near = c->pwd_row_cap, cap_sum = c->pwd_row_cap;
+    if (const int rc = pwd_grow(c, (void**)&c->d_pwd_near, &cap_near, (size_t)ma,
+                                2 * sizeof(int32_t), "nearest"))
+      return rc;
+    if (const int rc = pwd_grow(c, (void**)&c->d_pwd_rowsum, &cap_sum, (size_t)ma,
+                                sizeof(int64_t), "row sums")) {
+      // nearest is larger than recorded, which is harmless
+      return rc;
+    }
+    c->pwd_row_cap = (size_t)ma;
+  }
+  if (const int rc = pwd_upload(c, c->d_pwd_list[0], a, ma)) return rc;
+  if (!sym)
+    if (const int rc = pwd_upload(c, c->d_pwd_list[1], b, mb)) return rc;
+  const FwPwdPlan q = fw_pwd_plan(c->g->n, c->lb, fw_pairdist_env("FLIPWALK_PWD_TILE"),
+                                  fw_pairdist_env("FLIPWALK_PWD_CHUNK"));
+  FwPairdistParams p{};
+  p.labels = c->d_labels;
+  p.lab_stride = c->p.lab_stride;
+  p.a = c->d_pwd_list[0];
+  p.b = sym ? c->d_pwd_list[0] : c->d_pwd_list[1];
+  p.D = c->d_pwd_D;
+  p.ma = ma;
+  p.mb = mb;
+  p.symmetric = sym ? 1 : 0;
+  p.n = c->g->n;
+  p.lb = c->lb;
+  p.lab_words = (int)(((int64_t)c->g->n * c->lb + 31) / 32);
+  p.tile = q.tile;
+  p.chunk = q.chunk;
+  p.rs = q.rs;
+  p.n_chunks = q.n_chunks;
+  p.lds_bytes = q.lds_bytes;
+  // like the exchange, record, tally and census steps: the run timing events are left alone
+  int le = fw_launch_pairdist(p, c->stream);
+  if (le != 0)
+    return fail(FW_EHIP, "pair-distance launch failed: %s", hipGetErrorString((hipError_t)le));
+  FwPairdistReduceParams r{};
+  r.D = c->d_pwd_D;
+  r.rowsum = c->d_pwd_rowsum;
+  r.nearest = c->d_pwd_near;
+  r.hist = c->d_pwd_hist;
+  r.ma = ma;
+  r.mb = mb;
+  r.symmetric = p.symmetric;
+  r.n = p.n;
+  r.lds_bins = p.n + 1 <= 12288 ? p.n + 1 : 0;
+  le = fw_launch_pairdist_reduce(r, c->stream);
+  if (le != 0)
+    return fail(FW_EHIP, "pair-distance reduction launch failed: %s",
+                hipGetErrorString((hipError_t)le));
+  c->pwd_have = true;
+  c->pwd_sym = sym;
+  c->pwd_ma = ma;
+  c->pwd_mb = mb;
+  c->pwd_tile = q.tile;
+  c->pwd_chunk = q.chunk;
+  c->pwd_measured += 1;
+  return FW_OK;
+}
+
+int fw_chains_read_pairdist(fw_chains* c, int32_t what, void* dst, size_t bytes) {
+  if (!c) return fail(FW_EINVAL, "fw_chains_read_pairdist: null");
+  size_t need = 0;
+  if (const int rc = pwd_bytes(c, what, &need)) return rc;
+  if (what != FW_PAIRDIST_HIST && !c->pwd_have)
+    return fail(FW_ESTATE, "fw_chains_read_pairdist: nothing has been measured yet");
+  if (bytes < need || !dst) return fail(FW_EINVAL, "the pair distances need %zu bytes", need);
+  if (what == FW_PAIRDIST_HIST && !c->d_pwd_hist) {  // never measured, never written: all zero
+    std::memset(dst, 0, need);
+    return FW_OK;
+  }
+  HIPCHK(hipSetDevice(c->g->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const void* src = what == FW_PAIRDIST_MATRIX   ? (const void*)c->d_pwd_D
+                    : what == FW_PAIRDIST_ROWSUM ? (const void*)c->d_pwd_rowsum
+                    : what == FW_PAIRDIST_NEAREST ? (const void*)c->d_pwd_near
+                                                  : (const void*)c->d_pwd_hist;
+  HIPCHK(hipMemcpy(dst, src, need, hipMemcpyDeviceToHost));
+  return FW_OK;
+}
+
+int fw_chains_write_pairdist(fw_chains* c, int32_t what, const void* src, size_t bytes) {
+  if (!c) return fail(FW_EINVAL, "fw_chains_write_pairdist: null");
+  if (what != FW_PAIRDIST_HIST)
+    return fail(FW_EINVAL, "fw_chains_write_pairdist: only FW_PAIRDIST_HIST can be written (got %d)", what);
+  const size_t need = pwd_hist_bytes(c);
+  if (bytes < need || !src) return fail(FW_EINVAL, "the pair-distance histogram needs %zu bytes", need);
+  HIPCHK(hipSetDevice(c->g->device));
+  if (const int rc = pwd_ensure_hist(c)) return rc;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpy(c->d_pwd_hist, src, need, hipMemcpyHostToDevice));
+  return FW_OK;
+}
+
+int fw_chains_pairdist_reset(fw_chains* c) {
+  if (!c) return fail(FW_EINVAL, "null handle");
+  if (c->d_pwd_hist) {
+    HIPCHK(hipSetDevice(c->g->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemset(c->d_pwd_hist, 0, pwd_hist_bytes(c)));
+  }
+  c->pwd_measured = 0;
+  return FW_OK;
+}
+
+int fw_chains_pairdist_info(const fw_chains* c, int64_t info[7]) {
+  if (!c || !info) return fail(FW_EINVAL, "fw_chains_pairdist_info: null");
+  const FwPwdPlan q = fw_pwd_plan(c->g->n, c->lb, fw_pairdist_env("FLIPWALK_PWD_TILE"),
+                                  fw_pairdist_env("FLIPWALK_PWD_CHUNK"));
+  info[0] = c->pwd_ma;
+  info[1] = c->pwd_mb;
+  info[2] = c->pwd_sym ? 1 : 0;
+  info[3] = c->lb;
+  info[4] = c->pwd_measured;
+  info[5] = c->pwd_have ? c->pwd_tile : q.tile;
+  info[6] = c->pwd_have ? c->pwd_chunk : q.chunk;
   return FW_OK;
 }
 

@@ -407,6 +407,36 @@ int fw_census_env(const char* name);  // a test knob's value, -1 when unset
 int fw_launch_census(const FwCensusParams& p, void* stream);
 int fw_launch_census_add(const FwCensusAddParams& a, void* stream);
 
+// ---- pairwise plan distances between two lists of chains (fw_pairdist.hip) ------------------
+// fw_chains_pairdist_async, first kernel.  Workgroup (bx, by) owns the pairs of a-positions
+// [by tile, ..) and b-positions [bx tile, ..); in the symmetric case (b is a) only bx >= by
+// works, and an off-diagonal block also stores its transpose.  tile, chunk, rs: fw_pairdist_plan.h.
+struct FwPairdistParams {
+  const uint8_t* labels;   // packed lb-bit label records, chain c at labels + c * lab_stride
+  int64_t lab_stride;      // bytes, a multiple of 16
+  const int32_t* a;        // [ma] chain ids
+  const int32_t* b;        // [mb] chain ids (== a when symmetric)
+  int32_t* D;              // [ma][mb]
+  int32_t ma, mb, symmetric;
+  int32_t n, lb, lab_words;
+  int32_t tile, chunk, rs, n_chunks, lds_bytes;
+};
+
+// second kernel: one wave per row of D.  lds_bins: n + 1 when the workgroup counts its rows'
+// values in LDS before adding them to hist, 0 when it adds them to hist directly.
+struct FwPairdistReduceParams {
+  const int32_t* D;
+  int64_t* rowsum;              // [ma]
+  int32_t* nearest;             // [ma][2]
+  unsigned long long* hist;     // [n + 1]
+  int32_t ma, mb, symmetric, n, lds_bins;
+};
+
+// Host-side launchers implemented in fw_pairdist.hip.
+int fw_pairdist_env(const char* name);  // a test knob's value, -1 when unset
+int fw_launch_pairdist(const FwPairdistParams& p, void* stream);
+int fw_launch_pairdist_reduce(const FwPairdistReduceParams& r, void* stream);
+
 // Host-side launchers implemented in fw_resample.hip.
 int fw_launch_clone(const FwCloneParams& p, void* stream);
 int fw_launch_resample_map(const FwResampleParams& p, void* stream);

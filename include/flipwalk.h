@@ -721,6 +721,69 @@ int fw_chains_write_census(fw_chains* c, int32_t what, const void* src, size_t b
 int fw_chains_census_reset(fw_chains* c);
 int fw_chains_census_info(const fw_chains* c, int64_t info[5]);
 
+/* ---- pairwise plan distances between two lists of chains: matrix, row sums, nearest, histogram
+ * The tally, geometry and census steps reduce one plan each, and the overlap step compares a
+ * chain with its own reference or with one partner.  This step answers how far the plans of an
+ * ensemble are from each other: the matrix that embedding, clustering, medoids, two-sample
+ * tests between groups of chains and the count of distinct plans after a resample start from.
+ * It runs on the device and between launches, as those steps are placed, from the label records;
+ * no run kernel changes, and it only reads plans: it works on every label width, on both run
+ * kernels' records, under a ladder (by chain id; grouping by rung is the caller's, through
+ * fw_chains_rungs) and on cloned or resampled populations.
+ *
+ * fw_chains_pairdist_async: a is int32 [ma], b is int32 [mb], values chain ids in [0, n_chains),
+ * duplicates allowed; b == NULL means b = a (the symmetric case; mb is ignored).  The lists are
+ * validated on the host before the device is touched: FW_EINVAL for a NULL handle or a NULL a,
+ * ma < 1, mb < 1 with b given, or a value out of range; FW_EUNSUPPORTED for ma * mb > 2^28;
+ * FW_ENOMEM when a buffer cannot be grown (the handle keeps what it had).  The lists reach the
+ * device through two pinned staging slots with events (the host waits only for the copy that
+ * last used a slot); the call enqueues on the handle's stream with no stream wait and no host
+ * synchronisation, except that a call whose lists are longer than any before waits for the
+ * stream once before it lets the smaller buffers go.  fw_chains_last_kernel_ms is not touched.
+ * With X_c the current plan of chain c (stuck chains like any other):
+ *   D[i][j]     = #{v < n : X_{a_i}(v) != X_{b_j}(v)}                   int32 [ma][mb]
+ *                 districts are compared by name, as FW_OVERLAP_DIST compares them (the
+ *                 label-permutation-minimal distance stays on the host: plandist)
+ *   rowsum[i]   = sum over j of D[i][j]                                  int64 [ma]
+ *   nearest[i]  = (min over j of D[i][j], the lowest j attaining it)     int32 [ma][2]
+ *                 in the symmetric case position j = i is left out, by position and not by
+ *                 chain id, and with ma = 1 the entry is (-1, -1)
+ *   hist[d]    += #{(i, j) : D[i][j] = d}                                uint64 [n + 1]
+ *                 over the positions i < j in the symmetric case, over all (i, j) otherwise;
+ *                 accumulated over measurements until fw_chains_pairdist_reset
+ * and the host counter n_measured is incremented at enqueue.  A first kernel computes D in
+ * tile x tile blocks of pairs from bit planes of the label words staged in LDS (only the blocks
+ * on or above the diagonal in the symmetric case, stored to both D[i][j] and D[j][i]; the
+ * diagonal is the computed value, which is 0); a second reads D with one wave per row.  Every
+ * element of D, rowsum and nearest has one owning lane, ties in nearest go to the lowest j by a
+ * fixed reduction, and hist is summed with 64-bit integer atomics: no result depends on the
+ * tile, the chunk or the order of threads.  FLIPWALK_PWD_TILE (16, 32, 64) and
+ * FLIPWALK_PWD_CHUNK (32-node groups per staging step) force the blocking, for tests.
+ *
+ * fw_chains_read_pairdist synchronises, then copies what the last measurement left
+ * (FW_PAIRDIST_MATRIX, _ROWSUM, _NEAREST; FW_ESTATE before any measurement) or the accumulated
+ * FW_PAIRDIST_HIST (all zero before any); FW_EINVAL for another kind or a buffer that is too
+ * small.  fw_chains_write_pairdist restores FW_PAIRDIST_HIST (checkpoints; n_measured is not
+ * changed; FW_EINVAL for any other kind); fw_chains_pairdist_reset zeroes hist and n_measured.
+ * fw_chains_pairdist_info: info = {the last ma, the last mb, 1 if the last measurement was
+ * symmetric, label bits per node of the handle's plans, n_measured, the tile, the chunk (of the
+ * last measurement, or of the plan in force before any)}.  fw_chains_reset_observables and
+ * fw_chains_set_ladder leave all of this alone.  Left out: matched distances and the k x k table
+ * per pair on the device, distances to stored snapshots or across handles, weighted distances,
+ * grouping by rung on the device, merging across ranks.  (These entry points arrived in 0.7
+ * without a version bump; fw_build_info gained pwd=<sha256 of fw_pairdist.hip,
+ * fw_pairdist_planes.h and fw_pairdist_plan.h>.) */
+#define FW_PAIRDIST_MATRIX  0   /* int32 [ma][mb]  */
+#define FW_PAIRDIST_ROWSUM  1   /* int64 [ma]      */
+#define FW_PAIRDIST_NEAREST 2   /* int32 [ma][2]   */
+#define FW_PAIRDIST_HIST    3   /* uint64 [n + 1]  */
+int fw_chains_pairdist_async(fw_chains* c, const int32_t* a, int32_t ma, const int32_t* b,
+                             int32_t mb);
+int fw_chains_read_pairdist(fw_chains* c, int32_t what, void* dst, size_t bytes);
+int fw_chains_write_pairdist(fw_chains* c, int32_t what, const void* src, size_t bytes);
+int fw_chains_pairdist_reset(fw_chains* c);
+int fw_chains_pairdist_info(const fw_chains* c, int64_t info[7]);
+
 /* Read a map (FW_MAP_*) of chains [chain0, chain0 + n_chains) as int64
  * [n_chains][len], or with FW_MAP_SUM its sum over those chains [len]; len is
  * n_edges for FW_MAP_CUT_TIMES and n otherwise.  Values are current through the
