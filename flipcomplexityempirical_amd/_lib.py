@@ -36,6 +36,8 @@ CENSUS_NODES, CENSUS_EDGES, CENSUS_BOUNDARY = 1, 2, 4
 CENSUS_OCC, CENSUS_ECUT, CENSUS_BND, CENSUS_CNT = 1, 2, 4, 8
 PAIRDIST_MATRIX, PAIRDIST_ROWSUM, PAIRDIST_NEAREST, PAIRDIST_HIST = 0, 1, 2, 3
 PAIRDIST_MAX_PAIRS = 1 << 28
+COASSIGN_TOGETHER, COASSIGN_CNT, COASSIGN_NODES = 0, 1, 2
+COASSIGN_MAX_ELEMS = 1 << 28
 
 STATS_DTYPE = np.dtype(
     [
@@ -148,6 +150,12 @@ SIGNATURES = [
     ("fw_chains_write_pairdist", ctypes.c_int, [_P, _I32, _P, ctypes.c_size_t]),
     ("fw_chains_pairdist_reset", ctypes.c_int, [_P]),
     ("fw_chains_pairdist_info", ctypes.c_int, [_P, _P]),
+    ("fw_chains_enable_coassign", ctypes.c_int, [_P, _P, _I32]),
+    ("fw_chains_coassign_async", ctypes.c_int, [_P]),
+    ("fw_chains_read_coassign", ctypes.c_int, [_P, _I32, _P, ctypes.c_size_t]),
+    ("fw_chains_write_coassign", ctypes.c_int, [_P, _I32, _P, ctypes.c_size_t]),
+    ("fw_chains_coassign_reset", ctypes.c_int, [_P]),
+    ("fw_chains_coassign_info", ctypes.c_int, [_P, _P]),
     ("fw_chains_read_map", ctypes.c_int, [_P, _I32, _I32, _I32, _I32, _P, ctypes.c_size_t]),
     ("fw_eval_flips", ctypes.c_int,
      [_P, _P, _I32, _P, _P, _I32, _I64, _I64, _P, _P, _P, _P]),

@@ -277,6 +277,10 @@ class Chains:
         self._overlap_base = 0
         self._census_base = 0  # as _overlap_base, for the ensemble census
         self._pairdist_base = 0  # and for the pairwise plan distances
+        # enable_coassignment: the caller's node order as positions in the sorted list the
+        # handle holds (None: not enabled); _coassign_base as _census_base
+        self._coassign_order = None
+        self._coassign_base = 0
         # clone / resample: the round the next resample() takes by default, and the counts a
         # restored checkpoint started from (as _tally_base)
         self.resample_round = 0
@@ -387,6 +391,7 @@ class Chains:
         check(_lib.load().fw_chains_set_ladder(self._h, ptr(rows), ptr(logb), len(bases),
                                                ptr(s), ptr(r)))
         self.ladder_bases, self.set_of_chain, self.ladder_round = bases, s, 0
+        self._coassign_base = 0  # the handle re-sized and zeroed the co-assignment by rung
 
     @property
     def n_rungs(self) -> int:
@@ -413,7 +418,8 @@ class Chains:
     def run_tempered(self, steps_per_round: int, n_rounds: int, round0: Optional[int] = None,
                      max_retries: int = DEFAULT_MAX_RETRIES, record: bool = False,
                      tally: bool = False, geometry: bool = False,
-                     overlap: bool | str = False, census: bool = False) -> None:
+                     overlap: bool | str = False, census: bool = False,
+                     coassign: bool = False) -> None:
         """``n_rounds`` x (``steps_per_round`` steps, one exchange), enqueued back to back and
         waited for once.  Rounds are numbered from ``round0`` (default: where the last call
         stopped, ``ladder_round``), which fixes the parity and the draws of each exchange.
@@ -421,8 +427,9 @@ class Chains:
         its chain has just run on; with ``tally`` every round is run, tally, exchange, so a
         plan is counted under that rung too, and with ``geometry`` its districts are measured
         under it, and with ``overlap`` (True: against the reference, or "partner") its distance
-        is binned under it, and with ``census`` it enters the ensemble maps of that rung (run,
-        tally, geometry, overlap, census, record, exchange)."""
+        is binned under it, and with ``census`` it enters the ensemble maps of that rung, and
+        with ``coassign`` the co-assignment matrix of that rung (run, tally, geometry, overlap,
+        census, coassign, record, exchange)."""
         if self.ladder_bases is None:
             raise ValueError("run_tempered needs a ladder (set_ladder)")
         r0 = self.ladder_round if round0 is None else int(round0)
@@ -437,6 +444,8 @@ class Chains:
                 self.overlap("reference" if overlap is True else overlap)
             if census:
                 self.census()
+            if coassign:
+                self.coassign()
             if record:
                 self.record()
             check(L.fw_chains_exchange_async(self._h, r0 + i))
@@ -525,13 +534,14 @@ class Chains:
     def run_sampled(self, steps_per_sample: int, n_samples: int,
                     max_retries: int = DEFAULT_MAX_RETRIES, tally: bool = False,
                     geometry: bool = False, overlap: bool | str = False,
-                    census: bool = False, pairs=False) -> None:
+                    census: bool = False, pairs=False, coassign: bool = False) -> None:
         """``n_samples`` x (``steps_per_sample`` steps, one recorded sample), enqueued back to
         back and waited for once.  With ``tally`` every sample's plans are tallied as well, with
         ``geometry`` their districts are measured, with ``overlap`` (True: against the
         reference, or "partner") they are compared, with ``census`` they enter the ensemble maps,
-        with ``pairs`` (True: all chains, or a member list) their pairwise distances are measured
-        (run, tally, geometry, overlap, census, pairs, record)."""
+        with ``pairs`` (True: all chains, or a member list) their pairwise distances are measured,
+        with ``coassign`` they enter the node co-assignment matrix (run, tally, geometry, overlap,
+        census, coassign, pairs, record)."""
         L = _lib.load()
         for _ in range(int(n_samples)):
             check(L.fw_chains_run_async(self._h, int(steps_per_sample), int(max_retries)))
@@ -543,6 +553,8 @@ class Chains:
                 self.overlap("reference" if overlap is True else overlap)
             if census:
                 self.census()
+            if coassign:
+                self.coassign()
             if pairs is not False and pairs is not None:
                 self.pair_distances(None if pairs is True else pairs)
             self.record()
@@ -824,6 +836,75 @@ class Chains:
         check(_lib.load().fw_chains_census_reset(self._h))
         self._census_base = 0
 
+    # ------------------------------------------------------------- node co-assignment
+    def enable_coassignment(self, nodes=None) -> None:
+        """Keep, summed across the chains, how many plans put nodes u and v in the same district
+        (fw_chains_enable_coassign), for the distinct ``nodes`` in any order (``None``: all n);
+        under a ladder one matrix per rung.  The handle takes the list sorted; every read comes
+        back in the caller's order.  Zeroes the arrays and the count; repeated, it replaces the
+        node list.  ``ValueError`` for duplicates."""
+        if nodes is None:
+            check(_lib.load().fw_chains_enable_coassign(self._h, None, 0))
+            self._coassign_order = np.arange(self.dgraph.n)
+        else:
+            a = np.asarray(nodes).ravel()
+            if a.size < 1 or a.dtype.kind not in "iu":
+                raise ValueError("enable_coassignment: nodes must be a non-empty integer list")
+            srt, inverse = np.unique(a, return_inverse=True)
+            if srt.size != a.size:
+                raise ValueError("enable_coassignment: duplicate nodes")
+            srt = np.ascontiguousarray(srt, np.int32)
+            check(_lib.load().fw_chains_enable_coassign(self._h, ptr(srt), srt.size))
+            self._coassign_order = np.asarray(inverse).ravel()
+        self._coassign_base = 0
+
+    def coassign(self) -> None:
+        """Add every chain's current plan to the co-assignment matrix on the handle's stream,
+        behind the runs already there (fw_chains_coassign_async); no wait."""
+        check(_lib.load().fw_chains_coassign_async(self._h))
+
+    def coassign_info(self) -> dict:
+        info = np.zeros(7, np.int64)
+        check(_lib.load().fw_chains_coassign_info(self._h, ptr(info)))
+        return {"m": int(info[0]), "label_bits": int(info[1]), "n_groups": int(info[2]),
+                "n_measured": int(info[3]) + self._coassign_base, "tile": int(info[4]),
+                "chunk": int(info[5]), "staged": bool(info[6])}
+
+    def _read_coassign(self, what, arr):
+        check(_lib.load().fw_chains_read_coassign(self._h, what, ptr(arr), arr.nbytes))
+        return arr
+
+    def _coassign_perm(self, m):
+        """The caller's order as positions in the handle's sorted list (a list the handle took
+        some other way, a re-sized ladder's for one, reads in the handle's order)."""
+        o = self._coassign_order
+        return o if o is not None and o.size == m else np.arange(m)
+
+    def coassignment(self) -> np.ndarray:
+        """uint64 [n_groups, m, m]: plans of each group that put nodes i and j of the list (in
+        the order given to ``enable_coassignment``) in one district, over all measurements;
+        symmetric, the diagonal equal to ``coassign_counts()`` (``coassign`` turns it into
+        frequencies, cores and entropies)."""
+        info = self.coassign_info()
+        m = max(info["m"], 1)
+        t = self._read_coassign(_lib.COASSIGN_TOGETHER, np.empty((info["n_groups"], m, m), np.uint64))
+        o = self._coassign_perm(m)
+        return np.ascontiguousarray(t[:, o][:, :, o])
+
+    def coassign_counts(self) -> np.ndarray:
+        """uint64 [n_groups]: plans counted per group, over all measurements."""
+        return self._read_coassign(_lib.COASSIGN_CNT,
+                                   np.empty(self.coassign_info()["n_groups"], np.uint64))
+
+    def coassign_nodes(self) -> np.ndarray:
+        """int32 [m]: the node list, in the order given to ``enable_coassignment``."""
+        m = max(self.coassign_info()["m"], 1)
+        return self._read_coassign(_lib.COASSIGN_NODES, np.empty(m, np.int32))[self._coassign_perm(m)]
+
+    def coassign_reset(self) -> None:
+        check(_lib.load().fw_chains_coassign_reset(self._h))
+        self._coassign_base = 0
+
     # ------------------------------------------------------------- pairwise plan distances
     def pair_distances(self, a=None, b=None) -> None:
         """Measure the Hamming distances between the current plans of the chains ``a`` and the
@@ -940,12 +1021,13 @@ class Chains:
     def run_annealed(self, bases, steps_per_stage: int, resample: bool = True,
                      record: bool = False, tally: bool = False, geometry: bool = False,
                      overlap: bool | str = False, max_retries: int = DEFAULT_MAX_RETRIES,
-                     estimate: bool = True, census: bool = False, pairs=False):
+                     estimate: bool = True, census: bool = False, pairs=False,
+                     coassign: bool = False):
         """Population annealing over ``bases``: at stage s every chain's bound table becomes
         that of ``bases[s]`` (a one-row ``set_schedule``, which stays in force afterwards), the
         population is resampled from ``bases[s - 1]`` (s >= 1, with ``resample``) and runs
-        ``steps_per_stage`` steps; then tally, geometry, overlap, census, pairs (True: all chains,
-        or a member list: one symmetric ``pair_distances``), record as asked.  The
+        ``steps_per_stage`` steps; then tally, geometry, overlap, census, coassign, pairs (True: all
+        chains, or a member list: one symmetric ``pair_distances``), record as asked.  The
         population is taken to sit at ``bases[0]`` on entry.  With ``estimate`` each stage's
         ``resample_info`` is read (one wait per stage) and the result is {"log_weight": the
         stages' ``population.log_weight_mean``, "log_z": their sum, "ess": the stages' effective
@@ -972,6 +1054,8 @@ class Chains:
                 self.overlap("reference" if overlap is True else overlap)
             if census:
                 self.census()
+            if coassign:
+                self.coassign()
             if pairs is not False and pairs is not None:
                 self.pair_distances(None if pairs is True else pairs)
             if record:
@@ -1104,6 +1188,12 @@ class Chains:
         if pwd["n_measured"]:
             ck["pair_distance_hist"] = self.pair_distance_hist()
             ck["n_pair_distances"] = np.int64(pwd["n_measured"])
+        coa = self.coassign_info()
+        if coa["m"]:
+            ck["coassign_nodes"] = self.coassign_nodes()
+            ck["coassign_together"] = self.coassignment()
+            ck["coassign_counts"] = self.coassign_counts()
+            ck["n_coassigned"] = np.int64(coa["n_measured"])
         return ck
 
     def restore(self, ck: dict) -> None:
@@ -1247,6 +1337,19 @@ class Chains:
             check(L.fw_chains_write_pairdist(self._h, _lib.PAIRDIST_HIST, ptr(hist), hist.nbytes))
             self._pairdist_base = int(ck["n_pair_distances"]) - (
                 self.pair_distance_info()["n_measured"] - self._pairdist_base)
+        # the co-assignment after the ladder as well: its matrices are kept by rung.  The
+        # checkpoint holds the caller's order; the handle's is the sorted one.
+        if "coassign_nodes" in ck:
+            self.enable_coassignment(np.asarray(ck["coassign_nodes"]))
+            o = np.argsort(self._coassign_order)  # sorted position -> caller's position
+            t = np.ascontiguousarray(np.asarray(ck["coassign_together"], np.uint64)[:, o][:, :, o])
+            cnt = np.ascontiguousarray(ck["coassign_counts"], np.uint64)
+            info = self.coassign_info()
+            if t.shape != (info["n_groups"], info["m"], info["m"]) or cnt.shape != (info["n_groups"],):
+                raise ValueError("checkpoint of another co-assignment shape")
+            check(L.fw_chains_write_coassign(self._h, _lib.COASSIGN_TOGETHER, ptr(t), t.nbytes))
+            check(L.fw_chains_write_coassign(self._h, _lib.COASSIGN_CNT, ptr(cnt), cnt.nbytes))
+            self._coassign_base = int(ck["n_coassigned"])  # enable zeroed the handle's count
 
     def save_checkpoint(self, path: str) -> None:
         ck = self.checkpoint()

@@ -16,6 +16,7 @@
 
 #include "fw_internal.h"
 #include "fw_census_plan.h"
+#include "fw_coassign_plan.h"
 #include "fw_math.h"
 #include "fw_pairdist_plan.h"
 #include "fw_resample_limbs.h"
@@ -269,6 +270,12 @@ struct fw_chains {
   size_t pwd_stage_cap[2] = {0, 0};  // bytes
   hipEvent_t pwd_ev[2] = {nullptr, nullptr};
   int pwd_slot = 0;
+  // fw_chains_enable_coassign (coa.m == 0: off): the plan and, in FwCoassignParams' names, the
+  // arrays; coa_nodes is the list in force, d_coa[] = {ebit, twin, planes, together, cnt}
+  FwCoassignParams coa{};
+  int64_t coa_measured = 0;
+  std::vector<int32_t> coa_nodes;
+  void* d_coa[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
 };
 
 namespace {
@@ -591,6 +598,111 @@ int cen_array(const fw_chains* c, int32_t what, int64_t* off, int64_t* len) {
   return FW_OK;
 }
 
+// ---- node co-assignment (fw_chains_enable_coassign): plan and buffers of a handle with n_groups
+// groups for a validated node list, built aside so that on failure the handle keeps what it had
+struct CoaBuild {
+  FwCoassignParams p{};
+  void* buf[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // ebit, twin, planes, together, cnt
+};
+
+void coa_free(CoaBuild* b) {
+  for (void* x : b->buf)
+    if (x) (void)hipFree(x);
+  *b = CoaBuild{};
+}
+
+size_t coa_together_bytes(const FwCoassignParams& p) {
+  return sizeof(uint64_t) * (size_t)p.n_groups * (size_t)p.m * (size_t)p.m;
+}
+
+int coa_build(const fw_chains* c, const std::vector<int32_t>& nodes, int n_groups, CoaBuild* out) {
+  const int m = (int)nodes.size(), lb = c->lb, n = c->g->n;
+  if ((int64_t)n_groups * m * m > FW_COA_MAX_ELEMS)
+    return fail(FW_EUNSUPPORTED, "coassign: %d groups x %d x %d nodes exceed 2^28 elements", n_groups, m, m);
+  if ((int64_t)n * lb > 0xFFFFFFFFll)
+    return fail(FW_EUNSUPPORTED, "coassign: records of %lld label bits", (long long)n * lb);
+  FwCoassignParams p{};
+  p.m = m;
+  p.ms = (m + 3) / 4 * 4;
+  p.lb = lb;
+  p.lab_words = (int)(((int64_t)n * lb + 31) / 32);
+  p.n_groups = n_groups;
+  p.per_group = c->n_chains / n_groups;
+  const FwCoaPlan q = fw_coa_plan(p.per_group, lb, fw_coassign_env("FLIPWALK_COA_TILE"),
+                                  fw_coassign_env("FLIPWALK_COA_CHUNK"));
+  p.n_words = q.n_words;
+  p.tile = q.tile;
+  p.shift = q.shift;
+  p.chunk = q.chunk;
+  p.rs = q.rs;
+  p.n_chunks = q.n_chunks;
+  p.lds_bytes = q.lds_bytes;
+  // transpose tiles and the window of a record each one's nodes span
+  p.n_ttiles = fw_coa_tiles(m);
+  std::vector<int32_t> twin((size_t)p.n_ttiles * 2);
+  int wd_max = 0;
+  for (int t = 0; t < p.n_ttiles; ++t) {
+    int e0, en, wd0, wdn;
+    fw_coa_tile_window(nodes.data(), m, t, lb, &e0, &en, &wd0, &wdn);
+    twin[2 * (size_t)t] = wd0;
+    twin[2 * (size_t)t + 1] = wdn;
+    wd_max = std::max(wd_max, wdn);
+  }
+  p.staged = fw_coa_stage(wd_max, fw_coassign_env("FLIPWALK_COA_STAGE") != 0, &p.nw, &p.stride);
+  p.t_lds_bytes = p.staged ? 64 * p.nw * (p.stride + 1) * 4 : 0;
+  std::vector<uint32_t> ebit((size_t)m);
+  for (int j = 0; j < m; ++j)
+    ebit[j] = (uint32_t)((int64_t)nodes[j] * lb -
+                         (p.staged ? (int64_t)twin[2 * (size_t)(j / FW_COA_TT)] * 32 : 0));
+  const int64_t slots = (p.per_group + 63) / 64, spw = (slots + p.nw - 1) / p.nw;
+  if ((int64_t)p.n_ttiles * n_groups * spw >= (1ll << 31))
+    return fail(FW_EUNSUPPORTED, "coassign: %d tiles x %d groups x %lld member blocks", p.n_ttiles,
+                n_groups, (long long)spw);
+  CoaBuild b;
+  const size_t sz[5] = {sizeof(uint32_t) * ebit.size(), sizeof(int32_t) * twin.size(),
+                        sizeof(uint32_t) * (size_t)n_groups * p.n_words * lb * (size_t)p.ms,
+                        coa_together_bytes(p), sizeof(uint64_t) * (size_t)n_groups};
+  bool ok = true;
+  for (int i = 0; i < 5 && ok; ++i) ok = hipMalloc(&b.buf[i], sz[i]) == hipSuccess;
+  const bool up = ok && hipMemcpy(b.buf[0], ebit.data(), sz[0], hipMemcpyHostToDevice) == hipSuccess &&
+                  hipMemcpy(b.buf[1], twin.data(), sz[1], hipMemcpyHostToDevice) == hipSuccess &&
+                  hipMemset(b.buf[3], 0, sz[3]) == hipSuccess &&
+                  hipMemset(b.buf[4], 0, sz[4]) == hipSuccess;
+  if (!up) {
+    coa_free(&b);
+    (void)hipGetLastError();
+    return ok ? fail(FW_EHIP, "coassign upload failed")
+              : fail(FW_ENOMEM, "coassign of %d nodes, %d chains in %d groups", m, c->n_chains, n_groups);
+  }
+  p.ebit = static_cast<const uint32_t*>(b.buf[0]);
+  p.twin = static_cast<const int32_t*>(b.buf[1]);
+  p.planes = static_cast<uint32_t*>(b.buf[2]);
+  p.together = static_cast<uint64_t*>(b.buf[3]);
+  p.cnt = static_cast<uint64_t*>(b.buf[4]);
+  b.p = p;
+  *out = b;
+  return FW_OK;
+}
+
+// the step is switched off and its buffers freed
+void coa_disable(fw_chains* c) {
+  CoaBuild old;
+  for (int i = 0; i < 5; ++i) old.buf[i] = c->d_coa[i], c->d_coa[i] = nullptr;
+  coa_free(&old);
+  c->coa = FwCoassignParams{};
+  c->coa_nodes.clear();
+  c->coa_measured = 0;
+}
+
+// the handle takes a finished build for the list `nodes` (its previous one is freed)
+void coa_adopt(fw_chains* c, const CoaBuild& b, const std::vector<int32_t>& nodes) {
+  std::vector<int32_t> keep(nodes);  // nodes may be the handle's own list
+  coa_disable(c);
+  for (int i = 0; i < 5; ++i) c->d_coa[i] = b.buf[i];
+  c->coa = b.p;
+  c->coa_nodes.swap(keep);
+}
+
 }  // namespace
 
 extern "C" {
@@ -793,7 +905,8 @@ void fw_chains_destroy(fw_chains* c) {
                   c->d_rsm_lower, c->d_rsm_extra, c->d_rsm_info,
                   c->d_cen_graph[0], c->d_cen_graph[1], c->d_cen_graph[2], c->d_cen_part,
                   c->d_cen_acc, c->d_pwd_list[0], c->d_pwd_list[1], c->d_pwd_D, c->d_pwd_rowsum,
-                  c->d_pwd_near, c->d_pwd_hist};
+                  c->d_pwd_near, c->d_pwd_hist,
+                  c->d_coa[0], c->d_coa[1], c->d_coa[2], c->d_coa[3], c->d_coa[4]};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   for (int i = 0; i < 2; ++i) {
@@ -1592,6 +1705,15 @@ int fw_chains_set_ladder(fw_chains* c, const double* thr_rows, const double* log
   // and the census arrays, whose slices are planned per group
   CenBuild cen;
   if (c->cen.what && ok && cen_build(c, c->cen.what, n_rungs, &cen) != FW_OK) ok = false;
+  // and the co-assignment matrices; a group count that takes them past 2^28 elements switches
+  // the step off
+  CoaBuild coa;
+  bool coa_drop = false;
+  if (c->coa.m && ok) {
+    const int rc = coa_build(c, c->coa_nodes, n_rungs, &coa);
+    coa_drop = rc == FW_EUNSUPPORTED;
+    if (rc != FW_OK && !coa_drop) ok = false;
+  }
   void* d_thr = shared ? nb[8] : (void*)c->d_thr;
   void* d_thr53 = shared ? nb[9] : (void*)c->d_thr53;
   const bool up =
@@ -1613,6 +1735,7 @@ int fw_chains_set_ladder(fw_chains* c, const double* thr_rows, const double* log
     if (geo_hist) (void)hipFree(geo_hist);
     if (ovl_hist) (void)hipFree(ovl_hist);
     cen_free(&cen);
+    coa_free(&coa);
     return ok ? fail(FW_EHIP, "ladder upload failed")
               : fail(FW_ENOMEM, "ladder of %d rungs for %d chains", n_rungs, C);
   }
@@ -1638,6 +1761,10 @@ int fw_chains_set_ladder(fw_chains* c, const double* thr_rows, const double* log
     c->d_ovl_hist = ovl_hist;
   }
   if (cen.acc) cen_adopt(c, cen);
+  if (coa.p.m)
+    coa_adopt(c, coa, c->coa_nodes);
+  else if (coa_drop)
+    coa_disable(c);
   c->d_thr = static_cast<double*>(d_thr);
   c->d_thr53 = static_cast<uint64_t*>(d_thr53);
   c->p.thr = c->d_thr;
@@ -2887,6 +3014,121 @@ int fw_chains_census_info(const fw_chains* c, int64_t info[5]) {
   info[2] = c->n_rungs ? c->n_rungs : 1;
   info[3] = c->g->nnz / 2;
   info[4] = c->cen_measured;
+  return FW_OK;
+}
+
+// ---------------------------------------------------------------- node co-assignment
+int fw_chains_enable_coassign(fw_chains* c, const int32_t* nodes, int32_t m) {
+  if (!c) return fail(FW_EINVAL, "fw_chains_enable_coassign: null handle");
+  const int n = c->g->n;
+  std::vector<int32_t> list;
+  if (!nodes) {
+    list.resize((size_t)n);
+    for (int v = 0; v < n; ++v) list[v] = v;
+  } else {
+    if (m < 1) return fail(FW_EINVAL, "fw_chains_enable_coassign: m = %d < 1", m);
+    for (int j = 0; j < m; ++j) {
+      if (nodes[j] < 0 || nodes[j] >= n)
+        return fail(FW_EINVAL, "fw_chains_enable_coassign: node %d at %d outside [0, %d)", nodes[j], j, n);
+      if (j && nodes[j] <= nodes[j - 1])
+        return fail(FW_EINVAL, "fw_chains_enable_coassign: the list is not strictly ascending at %d", j);
+    }
+    list.assign(nodes, nodes + m);
+  }
+  const int n_groups = c->n_rungs ? c->n_rungs : 1;
+  if ((int64_t)n_groups * (int64_t)list.size() * (int64_t)list.size() > FW_COA_MAX_ELEMS)
+    return fail(FW_EUNSUPPORTED, "fw_chains_enable_coassign: %d groups x %zu x %zu nodes exceed 2^28 elements",
+                n_groups, list.size(), list.size());
+  HIPCHK(hipSetDevice(c->g->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  CoaBuild b;
+  if (const int rc = coa_build(c, list, n_groups, &b)) return rc;
+  coa_adopt(c, b, list);
+  return FW_OK;
+}
+
+int fw_chains_coassign_async(fw_chains* c) {
+  if (!c) return fail(FW_EINVAL, "null handle");
+  if (!c->coa.m) return fail(FW_ESTATE, "fw_chains_coassign_async: co-assignment is not enabled");
+  HIPCHK(hipSetDevice(c->g->device));
+  FwCoassignParams p = c->coa;
+  p.labels = c->d_labels;
+  p.lab_stride = c->p.lab_stride;
+  p.chain_of = c->n_rungs ? c->d_chain_of : nullptr;
+  // like the exchange, record, tally and census steps: the run timing events are left alone
+  int le = fw_launch_coassign_transpose(p, c->stream);
+  if (le != 0)
+    return fail(FW_EHIP, "coassign transpose launch failed: %s", hipGetErrorString((hipError_t)le));
+  le = fw_launch_coassign_product(p, c->stream);
+  if (le != 0)
+    return fail(FW_EHIP, "coassign product launch failed: %s", hipGetErrorString((hipError_t)le));
+  c->coa_measured += 1;
+  return FW_OK;
+}
+
+int fw_chains_read_coassign(fw_chains* c, int32_t what, void* dst, size_t bytes) {
+  if (!c) return fail(FW_EINVAL, "fw_chains_read_coassign: null");
+  if (!c->coa.m) return fail(FW_ESTATE, "fw_chains_read_coassign: co-assignment is not enabled");
+  const FwCoassignParams& p = c->coa;
+  size_t need = 0;
+  switch (what) {
+    case FW_COASSIGN_TOGETHER: need = coa_together_bytes(p); break;
+    case FW_COASSIGN_CNT: need = sizeof(uint64_t) * (size_t)p.n_groups; break;
+    case FW_COASSIGN_NODES: need = sizeof(int32_t) * (size_t)p.m; break;
+    default: return fail(FW_EINVAL, "unknown coassign array %d", what);
+  }
+  if (bytes < need || !dst) return fail(FW_EINVAL, "the coassign array needs %zu bytes", need);
+  HIPCHK(hipSetDevice(c->g->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (what == FW_COASSIGN_NODES)
+    std::memcpy(dst, c->coa_nodes.data(), need);
+  else
+    HIPCHK(hipMemcpy(dst, what == FW_COASSIGN_TOGETHER ? (const void*)p.together : (const void*)p.cnt,
+                     need, hipMemcpyDeviceToHost));
+  return FW_OK;
+}
+
+int fw_chains_write_coassign(fw_chains* c, int32_t what, const void* src, size_t bytes) {
+  if (!c) return fail(FW_EINVAL, "fw_chains_write_coassign: null");
+  if (!c->coa.m) return fail(FW_ESTATE, "fw_chains_write_coassign: co-assignment is not enabled");
+  const FwCoassignParams& p = c->coa;
+  size_t need = 0;
+  switch (what) {
+    case FW_COASSIGN_TOGETHER: need = coa_together_bytes(p); break;
+    case FW_COASSIGN_CNT: need = sizeof(uint64_t) * (size_t)p.n_groups; break;
+    case FW_COASSIGN_NODES:
+      return fail(FW_EINVAL, "fw_chains_write_coassign: the node list is set by fw_chains_enable_coassign");
+    default: return fail(FW_EINVAL, "unknown coassign array %d", what);
+  }
+  if (bytes < need || !src) return fail(FW_EINVAL, "the coassign array needs %zu bytes", need);
+  HIPCHK(hipSetDevice(c->g->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpy(what == FW_COASSIGN_TOGETHER ? (void*)p.together : (void*)p.cnt, src, need,
+                   hipMemcpyHostToDevice));
+  return FW_OK;
+}
+
+int fw_chains_coassign_reset(fw_chains* c) {
+  if (!c) return fail(FW_EINVAL, "null handle");
+  if (c->coa.m) {
+    HIPCHK(hipSetDevice(c->g->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemset(c->coa.together, 0, coa_together_bytes(c->coa)));
+    HIPCHK(hipMemset(c->coa.cnt, 0, sizeof(uint64_t) * (size_t)c->coa.n_groups));
+  }
+  c->coa_measured = 0;
+  return FW_OK;
+}
+
+int fw_chains_coassign_info(const fw_chains* c, int64_t info[7]) {
+  if (!c || !info) return fail(FW_EINVAL, "fw_chains_coassign_info: null");
+  info[0] = c->coa.m;
+  info[1] = c->lb;
+  info[2] = c->n_rungs ? c->n_rungs : 1;
+  info[3] = c->coa_measured;
+  info[4] = c->coa.tile;
+  info[5] = c->coa.chunk;
+  info[6] = c->coa.staged;
   return FW_OK;
 }
 

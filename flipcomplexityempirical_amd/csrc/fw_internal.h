@@ -437,6 +437,32 @@ int fw_pairdist_env(const char* name);  // a test knob's value, -1 when unset
 int fw_launch_pairdist(const FwPairdistParams& p, void* stream);
 int fw_launch_pairdist_reduce(const FwPairdistReduceParams& r, void* stream);
 
+// ---- node co-assignment across the chains (fw_coassign.hip) ---------------------------------
+// fw_chains_coassign_async.  First kernel: the labels of the listed nodes, transposed into bit
+// planes across the members of each group, planes[g][word][plane][entry] (rows of ms dwords);
+// workgroup (transpose tile, group, 64 nw members).  Second kernel: workgroup (bx, by, g) owns
+// the entry pairs [by tile, ..) x [bx tile, ..) of group g; only bx >= by works, and an
+// off-diagonal block also adds to the transposed element.  Member i of group g is chain
+// chain_of[i n_groups + g] under a ladder, else chain i.  Blocking: fw_coassign_plan.h.
+struct FwCoassignParams {
+  const uint8_t* labels;    // packed lb-bit label records, chain c at labels + c * lab_stride
+  int64_t lab_stride;       // bytes, a multiple of 16
+  const int32_t* chain_of;  // [per_group][n_groups] or null (no ladder)
+  const uint32_t* ebit;     // [m] bit offset of entry j's field in its tile's window
+  const int32_t* twin;      // [n_ttiles][2] {wd0, wdn} of a transpose tile (not staged: unused)
+  uint32_t* planes;         // [n_groups][n_words][lb][ms]
+  uint64_t* together;       // [n_groups][m][m]
+  uint64_t* cnt;            // [n_groups]
+  int32_t m, ms, lb, lab_words, n_groups, per_group, n_words;
+  int32_t n_ttiles, staged, nw, stride, t_lds_bytes;     // transpose
+  int32_t tile, shift, chunk, rs, n_chunks, lds_bytes;   // product (FwCoaPlan)
+};
+
+// Host-side launchers implemented in fw_coassign.hip.
+int fw_coassign_env(const char* name);  // a test knob's value, -1 when unset
+int fw_launch_coassign_transpose(const FwCoassignParams& p, void* stream);
+int fw_launch_coassign_product(const FwCoassignParams& p, void* stream);
+
 // Host-side launchers implemented in fw_resample.hip.
 int fw_launch_clone(const FwCloneParams& p, void* stream);
 int fw_launch_resample_map(const FwResampleParams& p, void* stream);

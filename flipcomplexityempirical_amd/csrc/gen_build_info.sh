@@ -16,8 +16,9 @@ O=$(cat fw_overlap.hip fw_overlap_bits.h | sha256sum | cut -c1-16)
 R=$(cat fw_resample.hip fw_resample_limbs.h | sha256sum | cut -c1-16)
 C=$(cat fw_census.hip fw_census_plan.h | sha256sum | cut -c1-16)
 P=$(cat fw_pairdist.hip fw_pairdist_planes.h fw_pairdist_plan.h | sha256sum | cut -c1-16)
+A=$(cat fw_coassign.hip fw_coassign_plan.h | sha256sum | cut -c1-16)
 B=$(cat fw_weights_bytes.h | sha256sum | cut -c1-16)
-printf 'extern "C" const char* fw_build_info(void) { return "src=%s flags=%s series=%s tally=%s geom=%s win=%s ovl=%s rsm=%s wb=%s cen=%s pwd=%s"; }\n' \
-  "$H" "$(echo $FLAGS)" "$S" "$T" "$G" "$W" "$O" "$R" "$B" "$C" "$P" > "$OUT.tmp"
+printf 'extern "C" const char* fw_build_info(void) { return "src=%s flags=%s series=%s tally=%s geom=%s win=%s ovl=%s rsm=%s wb=%s cen=%s pwd=%s coa=%s"; }\n' \
+  "$H" "$(echo $FLAGS)" "$S" "$T" "$G" "$W" "$O" "$R" "$B" "$C" "$P" "$A" > "$OUT.tmp"
 # rewrite only on change, so make relinks only when the provenance changes
 if ! cmp -s "$OUT.tmp" "$OUT" 2>/dev/null; then mv "$OUT.tmp" "$OUT"; else rm -f "$OUT.tmp"; fi

@@ -784,6 +784,77 @@ int fw_chains_write_pairdist(fw_chains* c, int32_t what, const void* src, size_t
 int fw_chains_pairdist_reset(fw_chains* c);
 int fw_chains_pairdist_info(const fw_chains* c, int64_t info[7]);
 
+/* ---- node co-assignment across the chains: the pair matrix of a node list, by rung -----------
+ * The census gives the one-point maps over the graph and fw_chains_pairdist_async the two-point
+ * function over plans.  This step gives the two-point function over nodes: how many plans of
+ * the ensemble put nodes u and v in the same district.  It is what cores (sets of nodes whose
+ * fate is tied) and consensus maps are read from, it shows which regions of a flip walk are
+ * frozen, and it is defined without reference to district names, so it keeps its meaning for
+ * k > 2, where occupancy is blurred by label symmetry.  It runs on the device and between
+ * launches, as the exchange, record, tally, geometry, overlap, census and pairdist steps are
+ * placed, from the label records; no run kernel changes, and it only reads plans: it works on
+ * every label width, on both run kernels' records, with the spatial maps enabled and on cloned
+ * or resampled populations.
+ *
+ * fw_chains_enable_coassign: nodes is int32 [m], strictly ascending, values in [0, n);
+ * nodes == NULL means all n nodes (m is ignored).  Everything is checked on the host before the
+ * device is touched: FW_EINVAL for a NULL handle, m < 1, a value out of range or a list that is
+ * not strictly ascending; FW_EUNSUPPORTED when n_groups * m * m > 2^28 (n_groups = n_rungs, or 1
+ * without a ladder); FW_ENOMEM when a buffer cannot be allocated (the handle keeps what it had).
+ * Allocates and zeroes the accumulators and zeroes n_measured; repeated, it replaces the node
+ * list.  The plan is derived here, once: tiles of 64 list entries with the window of label
+ * words each one's nodes span in a record, the member words of a group (32 members each), the
+ * tile of the pair blocks and the chunk of member words staged at a time.
+ *
+ * fw_chains_coassign_async (FW_ESTATE before fw_chains_enable_coassign) enqueues on the
+ * handle's stream, with no host synchronisation and without touching fw_chains_last_kernel_ms.
+ * Groups are the census's: member i of group g is chain chain_of[i * n_groups + g] under a
+ * ladder (the chain on rung g of set i, read on the device from the exchange step's own arrays:
+ * the host does not wait for them), else chain i; per_group = n_chains / n_groups.  With X_c the
+ * current plan of chain c (stuck chains like any other) it adds
+ *   cnt[g]            += per_group
+ *   together[g][i][j] += #{members c of g : X_c(nodes[i]) == X_c(nodes[j])}
+ * so the matrix is symmetric and its diagonal equals cnt[g].  The host counter n_measured is
+ * incremented at enqueue.  A first kernel transposes the labels of the listed nodes into bit
+ * planes across the members (member i at bit i % 32 of member word i / 32; bits past per_group
+ * zero), from label windows staged in LDS, or from the records in HBM where a tile's window is
+ * too long; a second takes tile x tile blocks of node pairs on or above the diagonal, walks the
+ * member words in chunks staged in LDS, counts per pair the differing members (XOR / OR /
+ * popcount over the planes, as the pairwise distance does over nodes) and adds per_group - diff
+ * to the uint64 accumulators, an off-diagonal block to both [i][j] and [j][i].  Every element
+ * has one owning lane and there are no atomics: no result depends on the tile, the chunk, the
+ * staging or the order of threads.  Counts of one measurement are 32 bits wide (per_group <
+ * 2^31).  FLIPWALK_COA_TILE (16, 32, 64), FLIPWALK_COA_CHUNK (member words per staging step) and
+ * FLIPWALK_COA_STAGE=0 (labels from HBM) force the plan, for tests; they are read at enable.
+ *
+ * fw_chains_read_coassign synchronises, then copies one array, accumulated over all
+ * measurements:
+ *   FW_COASSIGN_TOGETHER  uint64 [n_groups][m][m]
+ *   FW_COASSIGN_CNT       uint64 [n_groups]
+ *   FW_COASSIGN_NODES     int32 [m], the list in force (read only)
+ * FW_ESTATE before enable; FW_EINVAL for another kind or a buffer that is too small.
+ * fw_chains_write_coassign restores TOGETHER or CNT (checkpoints; n_measured is not changed;
+ * FW_EINVAL for NODES); fw_chains_coassign_reset zeroes the arrays and n_measured.
+ * fw_chains_coassign_info: info = {m (0: not enabled), label bits per node of the handle's
+ * plans, n_groups, n_measured, the node tile of a pair block, the member-word chunk, 1 if the
+ * label windows are staged in LDS}.  fw_chains_reset_observables leaves all of this alone;
+ * fw_chains_set_ladder on an enabled handle re-sizes the arrays for the new group count and
+ * zeroes them and n_measured, and switches the step off (as before enable) when the new size
+ * exceeds the 2^28 bound.  Left out: subsets or weights of chains, merging across ranks (the
+ * arrays are plain sums a caller can all-reduce), the k x k joint label table per node pair,
+ * clustering on the device (coassign.py reads cores from the matrix on the host).  (These entry
+ * points arrived in 0.7 without a version bump; fw_build_info gained coa=<sha256 of
+ * fw_coassign.hip and fw_coassign_plan.h>.) */
+#define FW_COASSIGN_TOGETHER 0  /* uint64 [n_groups][m][m] */
+#define FW_COASSIGN_CNT      1  /* uint64 [n_groups]       */
+#define FW_COASSIGN_NODES    2  /* int32 [m], read only    */
+int fw_chains_enable_coassign(fw_chains* c, const int32_t* nodes, int32_t m);
+int fw_chains_coassign_async(fw_chains* c);
+int fw_chains_read_coassign(fw_chains* c, int32_t what, void* dst, size_t bytes);
+int fw_chains_write_coassign(fw_chains* c, int32_t what, const void* src, size_t bytes);
+int fw_chains_coassign_reset(fw_chains* c);
+int fw_chains_coassign_info(const fw_chains* c, int64_t info[7]);
+
 /* Read a map (FW_MAP_*) of chains [chain0, chain0 + n_chains) as int64
  * [n_chains][len], or with FW_MAP_SUM its sum over those chains [len]; len is
  * n_edges for FW_MAP_CUT_TIMES and n otherwise.  Values are current through the
